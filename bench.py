@@ -2,6 +2,7 @@
 """bench.py -- CSR5 SpMV throughput on N MI355X GPUs of one node (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rmat24|scircuit|webbase|nd24k|rmat<S>]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one SpMV pass (one ``spmv()`` call: y = A*x) over the rank's matrix shard, with every input already
 resident in HBM.  The default workload is BASELINE.json configs[3], the configuration the metric spans: synthetic
@@ -13,15 +14,18 @@ the 1 -> 8 curve.  value = 2 * nnz_total * K / (max-over-ranks wall time of the 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (re-exec under torch.distributed.run);
 under a launcher (WORLD_SIZE set) it is one rank of N.
 
-The JSON line also carries:
-  roofline     -- algorithmic bytes per step / HIP-event time per step against the 8 TB/s HBM3E roof (the same
-                  figure from the wall clock is printed next to it: `frac_wall`)
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline keys, `config`, and `roofline`
+computed from the timed steps alone).  --dump-outputs DIR also writes y of the last timed step as DIR/*.npy (see
+dump_outputs).  Everything that takes runs or checks of its own is behind --full; with it the JSON line also carries:
+  roofline     -- side figures (x captured once per setX, narrowed values), the COLD protocol for a cache-sized working
+                  set, and the CSR -> CSR5 conversion figures (median of a few asCSR / asCSR5 rounds)
   cpu_baseline -- the reference's own CSR5_avx2 (oracle/_ref, kind "reference") or our C port of it (kind "port")
-                  timed on this node's host cores on the same matrix (rank 0, N = 1 only)
+                  timed on this node's host cores on the same matrix (rank 0; N > 1: also every rank's exact check and the
+                  whole matrix on rank 0's GPU under the same protocol)
   configs      -- (N = 1) the other BASELINE GPU configs (scircuit-like, webbase-like fp64; nd24k-like fp32), each
                   with a cache-WARM figure (back-to-back SpMVs on one matrix, as the reference CLI times them) and
                   a COLD one (the timed loop rotates over copies whose total footprint exceeds the 256-MiB Infinity
-                  Cache, so every SpMV streams from HBM)
+                  Cache, so every SpMV streams from HBM), and the locality-bracket points
 """
 from __future__ import annotations
 
@@ -41,6 +45,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 INFINITY_CACHE_BYTES = 256 * 1024 * 1024
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: all .npy files of one run together (below 64 MB with room to spare)
+DUMP_SAMPLE_SEED = 20240928  # fixes the sampled rows of an output larger than the budget
 
 
 def kernel_source_hash() -> str:
@@ -124,9 +130,14 @@ def parse_args():
                     help="scircuit / webbase: share of near-diagonal entries of the stand-in (defaults 0.5 / 0.3)")
     ap.add_argument("--values", default="int", choices=["int", "real"],
                     help="int = rand()%%10 (reference CLI data, exact); real = uniform(-1, 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: CPU baseline, sub-configs, locality points, "
+                         "cold protocol of cache-sized working sets, side figures, conversion time, N > 1 checks (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write y of the last step as DIR/*.npy (a fixed seeded sample beyond 60 MB)")
     ap.add_argument("--cold", action="store_true", help="time the headline workload with the cold-cache protocol too")
     ap.add_argument("--no-cold", action="store_true",
-                    help="skip the cold-cache protocol that a cache-sized working set gets by default (profiling runs: one protocol per trace)")
+                    help="--full: skip the cold-cache protocol that a cache-sized working set gets by default (profiling runs: one protocol per trace)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub-configs", action="store_true", help="skip the per-config array (N = 1)")
     ap.add_argument("--no-locality-points", action="store_true", help="skip the four locality-bracket points of the sub-configs")
@@ -273,15 +284,15 @@ class Problem:
         self.convert_first_ms = (time.perf_counter() - t0) * 1e3  # includes allocations and first-use code loading
         # steady-state conversion time: the reference CLI also converts back and forth before it times asCSR5
         # (CSR5_avx2/main.cpp:41-52: five asCSR5/asCSR rounds, then the timed one)
-        # -- median of a few rounds, one sample is at the mercy of the host
+        # -- median of a few rounds, one sample is at the mercy of the host (--full only: not part of the SpMV headline)
         samples = []
-        for _ in range(5 if self.nnz < 50_000_000 else 3):
+        for _ in range((5 if self.nnz < 50_000_000 else 3) if getattr(args, "full", True) else 0):
             _ck(A.asCSR(), "asCSR")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             _ck(A.asCSR5(), "asCSR5")  # returns after its one stream synchronisation
             samples.append((time.perf_counter() - t0) * 1e3)
-        self.convert_ms = sorted(samples)[len(samples) // 2]
+        self.convert_ms = sorted(samples)[len(samples) // 2] if samples else None
         self.info = A.info()
         if self.info.x_snapshot and hasattr(A, "snapshotX"):
             _ck(A.snapshotX(), "snapshotX")  # the permuted copy of x: once, here (behind the broadcast at N > 1), never inside a step
@@ -310,8 +321,11 @@ def timed(prob, steps, warmup, launch, dist=None):
     """W untimed steps, then EXACTLY K steps bracketed by barrier + synchronize.  Returns (wall_s, event_ms)."""
     import torch
     run_steps(prob, warmup, launch)
-    if launch == "graph":  # instantiate the graphs of the timed region outside it
-        run_steps(prob, steps, launch)
+    if launch == "graph":  # instantiate the graphs of the timed region outside it (one launch per distinct chunk length)
+        chunk = min(steps, 500)
+        run_steps(prob, chunk, launch)
+        if steps > chunk and steps % chunk:
+            run_steps(prob, steps % chunk, launch)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -324,6 +338,29 @@ def timed(prob, steps, warmup, launch, dist=None):
     if dist is not None:
         dist.barrier()
     return time.perf_counter() - t0, ev_ms
+
+
+def dump_outputs(out_dir, y, suffix="", budget=DUMP_BUDGET_BYTES) -> list:
+    """--dump-outputs: y of the last timed step (what a caller of spmv() receives) as <out_dir>/y<suffix>.npy in its own
+    dtype (fp64 / fp32).  A y larger than `budget` bytes is written as a fixed sample instead: the rows drawn without
+    replacement by a generator seeded with DUMP_SAMPLE_SEED, ascending, with their indices as y<suffix>_rows.npy (fp64,
+    exact below 2^53) -- the same rows in every run with the same arguments.  Returns the paths written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128  # per .npy file (format 1.0, 1-D array)
+    arrays = {}
+    if y.numel() * y.element_size() + header <= budget:
+        arrays["y"] = y.cpu().numpy()
+    else:
+        k = (budget - 2 * header) // (y.element_size() + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(y.numel(), size=k, replace=False))
+        arrays["y"] = y[torch.from_numpy(rows).to(y.device)].cpu().numpy()
+        arrays["y_rows"] = rows.astype(np.float64)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, name.replace("y", "y" + suffix, 1) + ".npy"))
+        np.save(paths[-1], a)
+    return paths
 
 
 def timed_cold(make_copy, base, steps, warmup):
@@ -372,7 +409,7 @@ def roofline_dict(prob, ev_ms_per_step, wall_ms_per_step, extra=None):
         "cache": ("working set far beyond the 256-MiB Infinity Cache: every step streams from HBM"
                   if prob.b_alg > 2 * INFINITY_CACHE_BYTES else
                   "WARM: the working set stays in the 256-MiB Infinity Cache between back-to-back steps (this figure is "
-                  "replaced by the COLD protocol's unless --no-cold)"),
+                  "replaced by the COLD protocol's under --full unless --no-cold)"),
     }
     if extra:
         d.update(extra)
@@ -430,7 +467,7 @@ def config_dict(prob, args, ingest_ms=None):
                        if info.x_snapshot else "every spmv (library default)") if info.slab_x_permuted else None,
         "values": "rand()%10 integers (reference CLI data, exact in fp)" if args.values == "int" else "uniform(-1,1)",
         "ingest_ms": ingest_ms,
-        "csr_to_csr5_ms": round(prob.convert_ms, 3),
+        "csr_to_csr5_ms": None if prob.convert_ms is None else round(prob.convert_ms, 3),
         "csr_to_csr5_first_call_ms": round(prob.convert_first_ms, 3),
     }
 
@@ -513,7 +550,9 @@ def sub_config(name, args, dev, band=None, far=None):
 
 # ----------------------------------------------------------------------------------------------------------
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become N ranks (one process per GPU) under torch.distributed.run."""
+    """`python bench.py --gpus N` without a launcher: start N ranks (one process per GPU) under torch.distributed.run in a
+    child process and exit with its status (this process has asked the runtime for the device count: it is not replaced)."""
+    import subprocess
     import torch
     ndev = torch.cuda.device_count()
     if ndev < args.gpus and os.environ.get("CSR5_BENCH_SHARE_GPU") != "1":
@@ -525,7 +564,7 @@ def self_launch(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -604,18 +643,23 @@ def main():
         x_broadcast_ms = (time.perf_counter() - t_b) * 1e3
     prob = Problem(mat, label, dtype_name, args, dev, args.seed + 13 + rank, x_dev=x_dev)
 
-    # correctness run (kept for the cpu_baseline comparison), then the timed region
-    _ck(prob.A.spmv(1.0, prob.yd), "spmv")
-    torch.cuda.synchronize()
-    y_first = prob.yd.cpu().numpy() if (rank == 0 or world > 1) else None
+    # --full: correctness run (kept for the cpu_baseline comparison), then the timed region
+    full = args.full
+    y_first = None
+    if full:
+        _ck(prob.A.spmv(1.0, prob.yd), "spmv")
+        torch.cuda.synchronize()
+        y_first = prob.yd.cpu().numpy() if (rank == 0 or world > 1) else None
     wall_s, ev_ms = timed(prob, steps, warmup, args.launch, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob.yd, "" if world == 1 else f"_rank{rank}", DUMP_BUDGET_BYTES // world)
 
     # N > 1: EVERY rank checks its own row block against the reference's compiled CSR5_avx2 (oracle/_ref; our C port of it
     # where that binary is absent) on the same block and the same x -- exact on the CLI's integer data -- all ranks at once,
     # each on its share of the host cores; the worst error of any rank goes into the line (all_reduce MAX)
     host = None
     check = None
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and full and not args.no_cpu_baseline:
         host = host_copy(prob)
         threads = max(1, min(32, (os.cpu_count() or 8) // world))
         try:
@@ -671,14 +715,14 @@ def main():
             roof["per_gpu_note"] = ("achieved/frac: rank 0's shard bytes (incl. the whole x it reads) over the "
                                     "max-over-ranks event time; largest shard = %d bytes; every rank's own figures: multi_gpu.ranks"
                                     % int(max_b_alg))
-        if world == 1 and (args.cold or (small_working_set(prob) and not args.no_cold)):
+        if world == 1 and (args.cold or (full and small_working_set(prob) and not args.no_cold)):
             cold_ms, k, cs = timed_cold(lambda: Problem(mat, label, dtype_name, args, dev, args.seed + 13), prob,
                                         steps, warmup)
             if small_working_set(prob):
                 roof = cold_is_the_number(prob, roof, ev_per_step, ms_per_step, cold_ms, k, cs)
             else:
                 roof["cold"] = cold_dict(prob, cold_ms, k, cs)
-        if world == 1 and info.slab_x_permuted and not info.x_snapshot and not args.no_side_figures:
+        if world == 1 and info.slab_x_permuted and not info.x_snapshot and full and not args.no_side_figures:
             # side figure: the same workload under the reference CLI's protocol -- setX once, then the timed loop -- with the
             # permuted copy of x taken once per setX (CSR5HIP_OPT_X_SNAPSHOT = 1, what ./spmv opts into)
             _ck(prob.A.setXSnapshot(1), "setXSnapshot")
@@ -696,7 +740,7 @@ def main():
             roof["x_protocol"] = ("NON-DEFAULT: CSR5HIP_OPT_X_SNAPSHOT = 1 (--x-snapshot 1): the permuted copy of x is taken once "
                                   "per setX, outside the timed steps")
         if (world == 1 and info.slab_hot and dtype_name == "f64" and not info.slab_values_narrowed and hasattr(prob.A, "setNarrowValues")
-                and not args.no_side_figures):
+                and full and not args.no_side_figures):
             # the same workload with CSR5HIP_OPT_NARROW_VALUES: the reference CLI's rand() % 10 values are exact in fp32, so
             # the slab kernel may stream them as fp32 (same result bit for bit).  NOT the headline: the roofline's algorithmic
             # bytes count the 8-byte value stream.
@@ -765,12 +809,13 @@ def main():
                            "roofline_frac": round(r[5] / (r[7] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if r[7] > 0 else None}
                           for r in per_rank],
             }
-        roof.update(conversion_roofline(prob, ev_per_step))
+        if full:
+            roof.update(conversion_roofline(prob, ev_per_step))
         if "x_snapshot_once_per_setX" in roof:
             roof["x_snapshot_frac"] = roof["x_snapshot_once_per_setX"]["frac"]
         if check is not None:
             out["multi_gpu"].update(check)
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             try:
                 if world == 1:
                     out["cpu_baseline"] = cpu_baseline(prob, y_first, args.cpu_seconds)
@@ -787,7 +832,7 @@ def main():
         del prob
         host = None
         torch.cuda.empty_cache()
-        if world > 1 and is_rmat and scaling == "strong" and not args.no_n1_leg:
+        if world > 1 and is_rmat and scaling == "strong" and full and not args.no_n1_leg:
             # rank 0 alone (the other ranks wait): the WHOLE matrix on this one GPU under the same protocol -> the speed-up of
             # this N-GPU line over N = 1 with no protocol difference booked as scaling; and CSR5_avx2 on the whole matrix
             try:
@@ -795,7 +840,7 @@ def main():
                                                          out.get("cpu_baseline")))
             except Exception as e:
                 out["multi_gpu"]["n1_same_protocol"] = {"error": repr(e)}
-        if world == 1 and not args.no_sub_configs and not real and args.workload == "rmat24":
+        if world == 1 and full and not args.no_sub_configs and not real and args.workload == "rmat24":
             subs = []
             for name in SUB_CONFIGS:
                 try:

@@ -55,7 +55,7 @@ def main():
             w.writerow(COLUMNS)
         for f in files:
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mtx", f, "--steps", str(args.steps), "--warmup",
-                   str(args.warmup), "--dtype", dtype_of.get(f, args.dtype), "--cpu-seconds", "2"]
+                   str(args.warmup), "--dtype", dtype_of.get(f, args.dtype), "--cpu-seconds", "2", "--full"]
             if args.no_cpu_baseline:
                 cmd.append("--no-cpu-baseline")
             out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)

@@ -54,7 +54,7 @@ for d in sorted(glob.glob(os.path.join(src, "profiles_*"))):
 json.dump(traffic, open(os.path.join(dst, f"{rnd}_traffic.json"), "w"), indent=1)
 with open(os.path.join(dst, f"{rnd}_summary.md"), "w") as f:
     f.write(f"# {rnd}: rocprofv3 summaries (MI355X, `scripts/gpu_profiles.sh`)\n\n"
-            "`*_kernel_stats.csv` = `rocprofv3 --kernel-trace --stats` of `python bench.py --no-cpu-baseline <args>`;\n"
+            "`*_kernel_stats.csv` = `rocprofv3 --kernel-trace --stats` of `python bench.py --full --no-cpu-baseline <args>`;\n"
             "traffic = (2*FETCH_SIZE + WRITE_SIZE) KiB from separate `--pmc` passes (see scripts/collect_profiles.py).\n\n"
             "| run | sigma | mode | k_spmv avg us (rocprof) | k_spmv min us | HIP-event us/launch (bench.py, same run) | B_alg MB | HBM-side traffic MB | L2 hit |\n|---|---|---|---|---|---|---|---|---|\n")
     for r in rows:

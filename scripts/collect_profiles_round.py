@@ -40,7 +40,7 @@ for f in sorted(glob.glob(os.path.join(src, "*_pmc.json"))):
 json.dump(traffic, open(os.path.join(dst, f"{ROUND}_traffic.json"), "w"), indent=1)
 with open(os.path.join(dst, f"{ROUND}_summary.md"), "w") as f:
     f.write(f"# {ROUND}: rocprofv3 summaries (MI355X, `scripts/gpu_profiles_round.sh`)\n\n"
-            f"`{ROUND}_<run>_kernel_stats.csv` = `rocprofv3 --kernel-trace --stats` of `python bench.py --no-cpu-baseline --no-sub-configs <args>`.\n"
+            f"`{ROUND}_<run>_kernel_stats.csv` = `rocprofv3 --kernel-trace --stats` of `python bench.py --full --no-cpu-baseline --no-sub-configs <args>`.\n"
             "Step time (rocprof) = sum over the step's kernels (tile kernel [+ tail / range-finish launch] [+ slab combine]) of average duration.\n"
             "traffic = (2*FETCH_SIZE + WRITE_SIZE) KiB per step from separate `--pmc` passes (counters only).\n"
             "Small workloads run with `--no-cold` here (one protocol per trace: cache-warm back-to-back steps); their HIP-event time under the\n"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of two library builds on the bench workloads: scripts/probes/libcsr5hip_prev.so vs the in-tree library
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q 2>&1 | tail -2
 for rep in 1 2 3; do
   for v in prev cur; do

@@ -1,5 +1,5 @@
 #!/bin/bash
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 for v in base nt base nt; do
   echo "== $v"
   if [ $v = nt ]; then export CSR5HIP_LIB=$PWD/scripts/probes/libcsr5hip_CSR5_NT_STREAM.so; else unset CSR5HIP_LIB; fi

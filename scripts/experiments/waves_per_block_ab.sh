@@ -1,5 +1,5 @@
 #!/bin/bash
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 for w in 4 2 3 4 2; do
   echo "== waves per workgroup $w"
   if [ $w != 4 ]; then export CSR5HIP_LIB=$PWD/scripts/probes/libcsr5hip_wpb$w.so; else unset CSR5HIP_LIB; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # waves per workgroup x sigma, several processes each (the step time has per-process modes)
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py | awk '{print $(NF-6)}'; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py | awk '{print $(NF-6)}'; }
 for s in 5 8; do
   for w in 1 2 4; do
     if [ $w = 2 ]; then unset CSR5HIP_LIB; else export CSR5HIP_LIB=$PWD/scripts/probes/libcsr5hip_wpb$w.so; fi

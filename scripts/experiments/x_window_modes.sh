@@ -1,5 +1,5 @@
 #!/bin/bash
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -3
 for xw in off force auto; do
 echo "== x-window $xw"

@@ -1,5 +1,5 @@
 #!/bin/bash
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 for rep in 1 2 3; do
   one
   one --x-window force

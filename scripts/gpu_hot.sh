@@ -1,6 +1,6 @@
 #!/bin/bash
 # LDS hot table of the slab kernel: parity tests, then bench lines hot on / off
-one() { python bench.py --no-cpu-baseline --no-sub-configs "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline --no-sub-configs "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 mkdir -p gpurun_out
 python - <<'PY'
 import torch

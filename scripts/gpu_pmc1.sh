@@ -5,7 +5,7 @@ OUT=$REPO/gpurun_out
 tag=$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 240 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/pmc1_${tag} -o p -- python $REPO/bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" > $OUT/pmc1_${tag}.log 2>&1
+timeout 240 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/pmc1_${tag} -o p -- python $REPO/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" > $OUT/pmc1_${tag}.log 2>&1
 f=$(find $OUT/pmc1_${tag} -name "*counter_collection.csv" | head -1)
 echo "== $tag: $PMC"
 [ -n "$f" ] && KFILTER=${KFILTER:-k_spmv} python3 - "$f" <<'PY'

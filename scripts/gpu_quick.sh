@@ -1,6 +1,6 @@
 #!/bin/bash
 # quick loop: parity tests, then bench lines for the main workloads
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 mkdir -p gpurun_out
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -5
 one --steps 1000; one --steps 1000 --mode two-pass

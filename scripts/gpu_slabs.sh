@@ -1,6 +1,6 @@
 #!/bin/bash
 # slab structure: parity tests, then bench lines with and without slabs
-one() { python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
+one() { python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python scripts/benchline.py; }
 mkdir -p gpurun_out
 timeout 1200 python -m pytest tests/test_gpu_slabs.py -x -q 2>&1 | tail -15
 one --workload webbase --steps 300 --slabs 0

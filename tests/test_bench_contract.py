@@ -23,9 +23,9 @@ def _run(*args, env=None, expect_rc=0):
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_keys():
-    """The driver's own command form.  The default workload is the BASELINE headline: R-MAT scale 24, fp64, whole
+    """The driver's command form with --full.  The default workload is the BASELINE headline: R-MAT scale 24, fp64, whole
     matrix on one GPU at N = 1, with the other GPU configs as a `configs` array (warm and cold figures)."""
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--full")
     assert "R-MAT scale 24" in d["config"]["workload"] and d["config"]["nnz_per_gpu"] == 268435456
     assert d["scaling"] == "strong"
     subs = d["configs"]
@@ -78,7 +78,7 @@ def test_bench_multi_gpu_form_launches_its_own_ranks():
     import torch
     if torch.cuda.device_count() < 2:
         _run("--gpus", "2", "--workload", "rmat16", "--steps", "5", "--warmup", "1", expect_rc=1)
-    d = _run("--gpus", "2", "--workload", "rmat18", "--steps", "10", "--warmup", "2",
+    d = _run("--gpus", "2", "--workload", "rmat18", "--steps", "10", "--warmup", "2", "--full",
              env={"CSR5_BENCH_SHARE_GPU": "1"} if torch.cuda.device_count() < 2 else None)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["config"]["nnz_per_gpu"] < (1 << 18) * 16, "rank 0 holds one row block, not the whole matrix"
@@ -124,7 +124,7 @@ def test_bench_eight_ranks_report_every_rank():
     hook, gloo) -- the control flow, the sharding and the per-rank report are the ones an 8-GPU node runs."""
     import torch
     shared = torch.cuda.device_count() < 8
-    d = _run("--gpus", "8", "--workload", "rmat20", "--steps", "10", "--warmup", "2",
+    d = _run("--gpus", "8", "--workload", "rmat20", "--steps", "10", "--warmup", "2", "--full",
              env={"CSR5_BENCH_SHARE_GPU": "1"} if shared else None)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong"
     _check_multi_gpu_keys(d, 8, 1 << 20)
@@ -140,7 +140,7 @@ def test_bench_picks_up_real_suitesparse_files(tmp_path):
     mtx = os.path.join(ROOT, "tests", "golden", "mtx")
     shutil.copy(os.path.join(mtx, "general_real.mtx"), tmp_path / "scircuit.mtx")
     shutil.copy(os.path.join(mtx, "symmetric_real.mtx"), tmp_path / "nd24k.mtx")
-    d = _run("--workload", "scircuit", "--steps", "20", "--warmup", "2", "--no-cpu-baseline", env={"CSR5_MTX_DIR": str(tmp_path)})
+    d = _run("--workload", "scircuit", "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--full", env={"CSR5_MTX_DIR": str(tmp_path)})
     assert "scircuit.mtx" in d["data"] and "suitesparse" in d["data"] and d["config"]["ingest_ms"] is not None
     assert "scircuit.mtx" in d["config"]["workload"]
     assert d["roofline"]["protocol"].startswith("cold") and "warm" in d["roofline"]
@@ -163,3 +163,63 @@ def test_real_file_lookup(tmp_path, monkeypatch):
     (tmp_path / "webbase-1M.mtx").write_text("%%MatrixMarket matrix coordinate real general\n1 1 1\n1 1 1.0\n")
     assert bench.real_file_for("webbase") == str(tmp_path / "webbase-1M.mtx")
     assert bench.real_file_for("rmat24") is None and bench.real_file_for("scircuit") is None
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline keys, times exactly --steps steps and leaves out every leg that takes runs
+    of its own; --dump-outputs writes y of the last timed step, the same in every run with the same arguments and the same
+    as what a --full run computes."""
+    import numpy as np
+    args = ("--gpus", "1", "--workload", "rmat16", "--steps", "7", "--warmup", "2")
+    d = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "GFLOPS" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2.0 * d["config"]["nnz_per_gpu"] / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]
+    for key in ("cpu_baseline", "configs", "value_multi_gpu_protocol"):
+        assert key not in d, key
+    assert "conversion_ms" not in d["roofline"] and "x_snapshot_once_per_setX" not in d["roofline"]
+    assert d["config"]["csr_to_csr5_ms"] is None
+    _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    _run(*args, "--dump-outputs", str(tmp_path / "c"), "--full", "--no-cpu-baseline")
+    assert sorted(os.listdir(tmp_path / "a")) == ["y.npy"]
+    ya = np.load(tmp_path / "a" / "y.npy")
+    assert ya.dtype == np.float64 and ya.shape == (d["config"]["m_per_gpu"],) and np.any(ya != 0)
+    for other in ("b", "c"):
+        assert np.array_equal(ya, np.load(tmp_path / other / "y.npy")), other
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path):
+    """CPU: y is written whole when it fits the budget, else as the same seeded sample of rows (with their indices) in
+    every call; dtypes are kept and the files stay within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    y = torch.arange(1000, dtype=torch.float32)
+    (p,) = bench.dump_outputs(str(tmp_path / "whole"), y)
+    assert p.endswith("y.npy") and np.array_equal(np.load(p), y.numpy()) and np.load(p).dtype == np.float32
+    y = torch.arange(100_000, dtype=torch.float64) * 3.0
+    budget = 64 * 1024
+    first = bench.dump_outputs(str(tmp_path / "s1"), y, "_rank1", budget)
+    second = bench.dump_outputs(str(tmp_path / "s2"), y, "_rank1", budget)
+    assert [os.path.basename(p) for p in first] == ["y_rank1.npy", "y_rank1_rows.npy"]
+    assert sum(os.path.getsize(p) for p in first) <= budget
+    ys, rows = np.load(first[0]), np.load(first[1])
+    assert ys.dtype == np.float64 and rows.dtype == np.float64 and ys.size == rows.size > 1000
+    assert np.all(np.diff(rows) > 0) and np.array_equal(ys, rows * 3.0)
+    for a, b in zip(first, second):
+        assert np.array_equal(np.load(a), np.load(b))
+
+
+def test_plain_is_the_default_and_full_is_opt_in(monkeypatch):
+    """CPU: `bench.py --gpus 1 --steps N --warmup W` is a plain run; --full and --dump-outputs are options."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"

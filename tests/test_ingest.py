@@ -11,6 +11,7 @@ GPU part (-m gpu): csr5hip_coo_to_csr / csr5hip_mtx_load against the oracle, bit
 (row_ptr, col_idx, val), plus size-independent properties on a large COO.
 """
 import glob
+import json
 import os
 
 import numpy as np
@@ -19,9 +20,12 @@ import pytest
 from benchmark_spmv_using_csr5_amd import _capi, ingest
 from benchmark_spmv_using_csr5_amd.matrices import MtxError
 from oracle.csr5_oracle import MtxExit, Oracle, Reference
+from oracle.gen_golden_records import cli_facts
 
 MTX_DIR = os.path.join(os.path.dirname(__file__), "golden", "mtx")
 EXPECTED = np.load(os.path.join(MTX_DIR, "expected.npz"))
+with open(os.path.join(os.path.dirname(__file__), "golden", "reference_records.json")) as _fh:
+    RECORDED_CLI = json.load(_fh)["cli"]
 FIXTURES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(MTX_DIR, "*.mtx")))
 GOOD = [f for f in FIXTURES if int(EXPECTED[f + ".code"]) == 0]
 BAD = [f for f in FIXTURES if int(EXPECTED[f + ".code"]) != 0]
@@ -73,27 +77,41 @@ def test_oracle_missing_file(oracle, tmp_path):
     assert e.value.code == -1
 
 
-@pytest.mark.skipif(not Reference.ingest_available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("name", GOOD)
 def test_oracle_ingest_matches_live_reference(oracle, name):
-    m, n, row_ptr, col, val = Reference().ingest(path_of(name))
+    """The live reference ingest where oracle/_ref is built (it must still give its recorded CSR, expected.npz), else that
+    recorded CSR."""
+    m, n, row_ptr, col, val = expected_csr(name)
+    if Reference.ingest_available():
+        lm, ln, lrp, lcol, lval = Reference().ingest(path_of(name))
+        assert (lm, ln) == (m, n) and np.array_equal(lrp, row_ptr) and np.array_equal(lcol, col), "stale expected.npz"
+        assert_same_values(lval, val)
     got = oracle.mtx_read(path_of(name))
     assert (got.m, got.n) == (m, n)
     assert np.array_equal(got.row_ptr, row_ptr) and np.array_equal(got.col, col)
     assert_same_values(got.val, val)
 
 
-@pytest.mark.skipif(not Reference.ingest_available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("name", [f for f in GOOD if f not in ("empty_matrix",)])
-def test_reference_cli_runs_on_the_fixtures(name):
+def test_reference_cli_runs_on_the_fixtures(oracle, name):
     """BASELINE.json configs[0] (plumbing + correctness baseline on the host CPU, no GPU): the reference's own CLI
-    -- ingest, CSR5_avx2 conversion, SpMV loop, self-check -- compiled from its sources where they lie, accepts
-    every fixture, reports the dimensions the goldens hold and passes its own check."""
+    -- ingest, CSR5_avx2 conversion, SpMV loop, self-check -- compiled from its sources where they lie (oracle/_ref), else
+    its recorded run (tests/golden/reference_records.json, oracle/gen_golden_records.py), accepts every fixture, reports
+    the dimensions the goldens hold and passes its own check; its dimensions and #partition are what the oracle reads and
+    builds."""
     m, n, row_ptr, col, val = expected_csr(name)
-    rc, text = Reference().cli(path_of(name))
-    assert rc == 0, text
-    assert f" ( {m}, {n} ) nnz = {col.size}\n" in text
-    assert "omega = 4, sigma = 16." in text and "Check... PASS!" in text
+    rec = RECORDED_CLI[name]
+    if Reference.ingest_available():
+        rc, text = Reference().cli(path_of(name))
+        assert rc == 0, text
+        assert f" ( {m}, {n} ) nnz = {col.size}\n" in text
+        assert "omega = 4, sigma = 16." in text and "Check... PASS!" in text
+        assert cli_facts(text) == rec["lines"], "stale record: re-run oracle/gen_golden_records.py"
+    assert rec["rc"] == 0 and f" ( {m}, {n} ) nnz = {col.size}" in rec["lines"] and "Check... PASS!" in rec["lines"]
+    got = oracle.mtx_read(path_of(name))
+    assert (got.m, got.n, got.nnz) == (m, n, col.size)
+    p = oracle.convert(4, 16, m, got.row_ptr, got.col, got.val).p
+    assert f"omega = 4, sigma = 16. #partition = {p}" in rec["lines"], (p, rec["lines"])
 
 
 # ---------------------------------------------------------------------------------------------
