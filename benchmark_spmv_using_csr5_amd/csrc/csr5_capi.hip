@@ -127,6 +127,7 @@ struct csr5hip_handle_s {
     int col31_request = 1;       // CSR5HIP_OPT_FLAGGED_COLUMNS: 0 off, 1 auto (default), 2 force
     bool col31_built = false;
     Buffer b_col31;              // [(p-1) * T words]
+    Buffer b_spmm;               // csr5hip_spmm: carries of one column block, p x spmm_block_width(k) values (first call that needs it)
     double wall_clock_khz = 0;         // rate of the device's constant wall clock (phase stamps)
     double t_malloc = 0, t_tile_ptr = 0, t_tile_desc = 0, t_transpose = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -262,6 +263,7 @@ int csr5hip_free(csr5hip_handle h)
     h->b_arena.release();
     h->b_col16.release();
     h->b_col31.release();
+    h->b_spmm.release();
     if (h->host_words)
         (void)hipHostFree(h->host_words);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1558,6 +1560,7 @@ int csr5hip_as_csr(csr5hip_handle h)
     deactivate_slabs(h);
     HIP_TRY(launch_transpose(h->g, h->d, h->value_type, false, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->b_spmm.release(); // (the SpMM workspace is sized by the converted matrix: released with it)
     // the aux buffers stay cached in the handle (capacity only grows) until csr5hip_free
     h->format = CSR5HIP_FORMAT_CSR;
     return CSR5HIP_SUCCESS;
@@ -1578,6 +1581,31 @@ int csr5hip_spmv(csr5hip_handle h, double alpha, void *d_y)
         return CSR5HIP_INVALID_ARGUMENT;
     HIP_TRY(ensure_x_snapshot(h, h->stream));
     HIP_TRY(enqueue_spmv(h, d_y, h->stream, false));
+    return CSR5HIP_SUCCESS;
+}
+
+// Y = A * X for k dense vectors (csr5_spmm.hip).  Runs on the handle's own tile structure whatever path spmv() takes (column
+// slabs, hot table, x-window, fused mode ...): per column bit-identical to the two-pass spmv().  Reads neither the handle's x
+// nor its snapshot.  The carry workspace is allocated by the first call that needs it; later calls only enqueue.
+int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy)
+{
+    if (!h || k < 0 || ldx < k || ldy < k || (k > 0 && (!d_X || !d_Y)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (k == 0)
+        return CSR5HIP_SUCCESS;
+    const size_t work = (size_t)(h->g.p > 0 ? h->g.p : 1) * spmm_block_width(k) * h->vsize();
+    if (h->b_spmm.cap < work) {
+        const hipError_t e = h->b_spmm.reserve(work);
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); // (clear the sticky allocation error: the handle stays usable for spmv)
+            return fail_hip(e, "csr5hip_spmm: workspace");
+        }
+    }
+    HIP_TRY(launch_spmm(h->g, h->d, h->value_type, d_X, ldx, k, d_Y, ldy, h->b_spmm.ptr, h->zero_empty, h->opt.xcd_remap, h->stream));
     return CSR5HIP_SUCCESS;
 }
 

@@ -213,6 +213,11 @@ struct HotParams {
 constexpr int hot_child_sigma(int value_size) { return HOT_WAVE_LDS / (OMEGA * value_size); }
 hipError_t launch_spmv(const Geometry &g, const DeviceArrays &d, int value_type, const void *x,
                        void *y, const SpmvOptions &opt, hipStream_t s);
+// csr5_spmm.hip: Y = A * X for k dense vectors (row-major, leading dimensions ldx / ldy) on the plain tile structure, per column
+// bit-identical to the two-pass SpMV; `work` holds the carries of one column block: p x spmm_block_width(k) values
+hipError_t launch_spmm(const Geometry &g, const DeviceArrays &d, int value_type, const void *X, int ldx, int k, void *Y, int ldy,
+                       void *work, int zero_empty, int xcd_remap, hipStream_t s);
+constexpr int spmm_block_width(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

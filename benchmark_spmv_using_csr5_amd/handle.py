@@ -58,6 +58,7 @@ class anonymouslibHandle:
         if err:
             raise RuntimeError(f"csr5hip_create -> {err}")
         self._keep = {}  # borrowed tensors, kept alive while the handle points at them
+        self._m, self._n = int(m), int(n)
         if stream is not None:
             self.setStream(stream)
 
@@ -88,6 +89,37 @@ class anonymouslibHandle:
 
     def destroy(self) -> int:
         return self._lib.csr5hip_destroy(self._h)
+
+    def spmm(self, X, Y) -> int:
+        """Y = A * X for k dense vectors (csr5hip.h csr5hip_spmm): X (n, k) and Y (m, k) device tensors of the handle's
+        dtype with stride(1) == 1; the leading dimensions are their stride(0).  Column c of Y equals a two-pass spmv() of
+        X[:, c], bit for bit.  Wrong dtype, device, shape or inner stride raise ValueError before the library is called."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        for name, t, rows in (("X", X, self._n), ("Y", Y, self._m)):
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"spmm: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"spmm: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 2 or t.shape[0] != rows:
+                raise ValueError(f"spmm: {name} must have shape ({rows}, k), not {tuple(t.shape)}")
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError(f"spmm: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                raise ValueError(f"spmm: {name} rows overlap (stride(0) {t.stride(0)} < k = {t.shape[1]})")
+            if t.device.type != "cuda":
+                raise ValueError(f"spmm: {name} must live on the GPU, not {t.device}")
+        if X.shape[1] != Y.shape[1]:
+            raise ValueError(f"spmm: X has {X.shape[1]} columns, Y {Y.shape[1]}")
+        if X.device != Y.device:
+            raise ValueError(f"spmm: X on {X.device}, Y on {Y.device}")
+        k = int(X.shape[1])
+        ldx = max(int(X.stride(0)), k) if X.shape[0] > 1 else k
+        ldy = max(int(Y.stride(0)), k) if Y.shape[0] > 1 else k
+        return self.spmm_ptr(X, ldx, k, Y, ldy)
+
+    def spmm_ptr(self, X, ldx: int, k: int, Y, ldy: int) -> int:
+        """csr5hip_spmm on raw device pointers (or tensors): X with leading dimension ldx, Y with ldy"""
+        return self._lib.csr5hip_spmm(self._h, _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy))
 
     # -- additions (documented in include/csr5hip.h) ---------------------------------------------
     def spmv_repeat(self, alpha, y, count: int) -> int:
@@ -239,6 +271,7 @@ class anonymouslibHandle:
             raise RuntimeError(f"csr5hip_load -> {err}: {_capi.last_error()}")
         self = cls.__new__(cls)
         self._lib, self._h, self._vt, self._keep = lib, h, int(raw.value_type), {}
+        self._m, self._n = int(raw.m), int(raw.n)
         self.arrays = DeviceCsr(raw)
         return self
 

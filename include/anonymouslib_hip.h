@@ -133,6 +133,11 @@ public:
     {
         return _h ? csr5hip_spmv_repeat(_h, (double)alpha, (void *)y, count) : _err;
     }
+    // extension: Y = A * X for k dense vectors, row-major X (n x k, leading dimension ldx) and Y (m x k, ldy); device pointers
+    int spmm(const ANONYMOUSLIB_VT *X, int ldx, int k, ANONYMOUSLIB_VT *Y, int ldy)
+    {
+        return _h ? csr5hip_spmm(_h, (const void *)X, ldx, k, (void *)Y, ldy) : _err;
+    }
     int autotuneSigma(ANONYMOUSLIB_VT *y, int *sigma = 0, double *us = 0)
     {
         return _h ? csr5hip_autotune_sigma(_h, (void *)y, sigma, us) : _err;

@@ -208,6 +208,17 @@ int csr5hip_as_csr(csr5hip_handle h);
  * Every row that owns a non-zero, and every row >= tail_partition_start, is overwritten; other
  * (empty) rows are left untouched.  Unlike the CUDA variant y need not be zeroed by the caller. */
 int csr5hip_spmv(csr5hip_handle h, double alpha, void *d_y);
+/* Extension (not in the reference): Y = A*X for k dense vectors.  X: n rows x k, row-major, leading dimension ldx >= k
+ * (element (j, c) at X[j*ldx + c]); Y: m rows x k, row-major, ldy >= k.  Device pointers, element-aligned.  Asynchronous on
+ * the handle's stream.  Per column c < k, the rows of Y written are spmv()'s (every row that owns a non-zero and every row
+ * >= tail_partition_start; the other empty rows only with CSR5HIP_OPT_ZERO_EMPTY_ROWS); columns k .. ldy-1 are never written.
+ * Column c is bit-identical to a two-pass spmv() (CSR5HIP_OPT_SPMV_MODE = 0, no column slabs) with x = X[:, c], whatever
+ * options the handle carries.  No alpha; the handle's x is neither needed nor touched.  k = 0 is a no-op.  The carry
+ * workspace (p tiles x min(8, k rounded up to 1, 2, 4, 8) values) is allocated by the first call that needs it and released by
+ * asCSR / destroy / free; later calls with the same k only enqueue work (capturable in a caller's graph).
+ * Returns CSR5HIP_INVALID_ARGUMENT for k < 0, ldx < k, ldy < k or null pointers with k > 0, CSR5HIP_UNSUPPORTED_CSR_SPMV
+ * in CSR format, CSR5HIP_UNKOWN_FORMAT before inputCSR. */
+int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
