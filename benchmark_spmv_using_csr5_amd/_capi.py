@@ -67,6 +67,8 @@ class Csr5Info(C.Structure):
         ("carries_deferred", C.c_int),
         ("narrow_columns", C.c_int),
         ("flagged_columns", C.c_int),
+        ("lds_y", C.c_int),
+        ("stream_nt", C.c_int),
     ]
 
 

@@ -1841,7 +1841,7 @@ int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info)
     info->x_window_tiles = h->xwin_tiles;
     info->x_window_lines = h->xwin_tiles > 0 ? (int)(h->xwin_lines / h->xwin_tiles) : 0;
     info->x_window_cover_pct = h->g.p > 1 ? (int)(h->xwin_covered * 100 / ((long long)(h->g.p - 1) * h->g.tile_elems)) : 0;
-    info->x_window_active = h->opt.x_window;
+    info->x_window_active = h->opt.x_window && h->opt.mode == 1 ? 1 : 0; // the two-pass kernel has no x-window variant
     info->t_malloc_ms = h->t_malloc;
     info->t_tile_ptr_ms = h->t_tile_ptr;
     info->t_tile_desc_ms = h->t_tile_desc;
@@ -1860,8 +1860,12 @@ int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info)
     info->x_snapshot = h->x_snapshot;
     info->slab_values_narrowed = h->slab_S > 0 && h->values_narrowed ? 1 : 0;
     info->carries_deferred = h->format == CSR5HIP_FORMAT_CSR5 && h->slab_S <= 0 && h->g.defer ? 1 : 0;
-    info->narrow_columns = h->format == CSR5HIP_FORMAT_CSR5 && h->slab_S <= 0 && h->opt.col16 && h->opt.x_window ? 1 : 0;
+    info->narrow_columns = h->format == CSR5HIP_FORMAT_CSR5 && h->slab_S <= 0 && h->opt.col16 && h->opt.x_window && h->opt.mode == 1 ? 1 : 0;
     info->flagged_columns = h->format == CSR5HIP_FORMAT_CSR5 && h->slab_S <= 0 && h->opt.col31 && !h->opt.x_window && h->opt.mode == 1 ? 1 : 0;
+    // the kernel variants launch_sigma() picks: compile-time sigma 4..32 only (the run-time-sigma kernel has neither)
+    const bool plain_ct = h->format == CSR5HIP_FORMAT_CSR5 && h->slab_S <= 0 && h->g.sigma >= 4 && h->g.sigma <= CSR5HIP_MAX_SIGMA;
+    info->lds_y = plain_ct && h->opt.lds_y && (size_t)OMEGA * h->g.sigma * h->vsize() <= 8192 ? 1 : 0;
+    info->stream_nt = plain_ct && h->opt.stream_nt && h->opt.mode == 1 && !h->opt.x_window ? 1 : 0;
     long long bytes = (long long)h->b_arena.cap;
     for (const Buffer *b : {&h->b_row_ptr2, &h->b_col2, &h->b_val2, &h->b_val32, &h->b_P, &h->b_rowidx, &h->b_base, &h->b_nonempty,
                             &h->b_hot_cols, &h->b_hot_count, &h->b_hot_tile0, &h->b_slab_off, &h->b_lead, &h->b_range_head, &h->b_slab_tmp,

@@ -182,6 +182,8 @@ typedef struct csr5hip_info {
     int carries_deferred;          /* 1 = cut rows are finished by a second small launch (CSR5HIP_OPT_DEFER_CARRIES)             */
     int narrow_columns;            /* 1 = the x-window kernel streams 16-bit column codes (CSR5HIP_OPT_NARROW_COLUMNS)            */
     int flagged_columns;           /* 1 = the plain kernel streams column words with the row-start flag in bit 31 (CSR5HIP_OPT_FLAGGED_COLUMNS) */
+    int lds_y;                     /* 1 = the plain kernel compacts y segments in LDS (CSR5HIP_OPT_LDS_Y and 64*sigma*sizeof(vT) <= 8 KiB) */
+    int stream_nt;                 /* 1 = the plain fused kernel streams column_index / value with non-temporal loads (CSR5HIP_OPT_STREAM_NT) */
 } csr5hip_info;
 
 /* anonymouslibHandle(m, n) -- anonymouslib_cuda.h:15.  Uses the current HIP device. */
