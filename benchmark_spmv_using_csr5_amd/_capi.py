@@ -116,6 +116,7 @@ SYMBOLS = [
     ("csr5hip_as_csr", C.c_int, [_H]),
     ("csr5hip_spmv", C.c_int, [_H, C.c_double, C.c_void_p]),
     ("csr5hip_spmm", C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("csr5hip_update_values", C.c_int, [_H, C.c_void_p]),
     ("csr5hip_spmv_repeat", C.c_int, [_H, C.c_double, C.c_void_p, C.c_int]),
     ("csr5hip_spmv_rotate", C.c_int, [C.POINTER(_H), C.POINTER(C.c_void_p), C.c_int, C.c_double, C.c_int]),
     ("csr5hip_snapshot_x", C.c_int, [_H]),
@@ -150,6 +151,7 @@ SYMBOLS = [
     ("csr5hip_multi_set_option", C.c_int, [_H, C.c_int, C.c_int]),
     ("csr5hip_multi_as_csr5", C.c_int, [_H]),
     ("csr5hip_multi_set_x", C.c_int, [_H, C.c_void_p]),
+    ("csr5hip_multi_update_values", C.c_int, [_H, C.c_void_p]),
     ("csr5hip_multi_spmv", C.c_int, [_H, C.c_double]),
     ("csr5hip_multi_spmv_repeat", C.c_int, [_H, C.c_double, C.c_int]),
     ("csr5hip_multi_synchronize", C.c_int, [_H]),

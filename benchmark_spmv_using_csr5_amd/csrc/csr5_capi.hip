@@ -160,6 +160,10 @@ struct csr5hip_handle_s {
     bool values_narrowed = false;
     bool xperm_valid = false; // (snapshot mode) the copy holds the current x
     int cold_total = 0;       // entries of the cold region
+    // csr5hip_update_values: source map of the slab child (csr5_refresh.hip), 4 bytes per non-zero, built by the first update after
+    // a conversion (it depends on the column indices only) and released with the slab structure
+    Buffer b_refresh_map;
+    bool refresh_map_valid = false;
 
     // csr5hip_spmv_rotate: one graph over several handles (cold-cache measurement protocol)
     hipGraphExec_t rotate_exec = nullptr;
@@ -849,6 +853,8 @@ static void release_slabs(csr5hip_handle h)
         h->slab_child = nullptr;
     }
     h->values_narrowed = false;
+    h->refresh_map_valid = false;
+    h->b_refresh_map.release();
     for (Buffer *b : {&h->b_row_ptr2, &h->b_col2, &h->b_val2, &h->b_val32, &h->b_P, &h->b_rowidx, &h->b_base, &h->b_nonempty, &h->b_col_lo, &h->b_col_hi, &h->b_hot_cols,
                       &h->b_hot_count, &h->b_hot_tile0, &h->b_slab_off, &h->b_lead, &h->b_range_head, &h->b_slab_tmp, &h->b_cold_base, &h->b_cold_cols,
                       &h->b_xperm})
@@ -870,6 +876,7 @@ static void deactivate_slabs(csr5hip_handle h)
     h->slab_S = 0;
     h->slab_m2 = 0;
     h->hot_cover_pct = 0;
+    h->refresh_map_valid = false; // (the next structure may partition other columns: the map is rebuilt by the next update)
 }
 
 // Number of slabs spmv() should use (0 = none).  Auto rule (measured on MI355X, scripts/experiments/slab_*):
@@ -1609,6 +1616,108 @@ int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, i
     return CSR5HIP_SUCCESS;
 }
 
+// ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
+// The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
+// again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.
+static int build_refresh_map(csr5hip_handle h)
+{
+    const Geometry &g = h->g;
+    const csr5hip_handle c = h->slab_child;
+    if (stream_is_capturing(h->stream)) {
+        g_last_error = "csr5hip_update_values: the first call after a conversion builds the slab child's source map and cannot be "
+                       "captured: call it once outside the capture";
+        return CSR5HIP_HIP_ERROR;
+    }
+    size_t tmp_bytes = 0;
+    hipError_t e = refresh_map_tmp_bytes(g.nnz, c->d.slab_bits, &tmp_bytes);
+    Buffer tmp;
+    if (e == hipSuccess)
+        e = h->b_refresh_map.reserve((size_t)g.nnz * 4);
+    if (e == hipSuccess)
+        e = tmp.reserve(tmp_bytes);
+    if (e == hipSuccess)
+        e = refresh_build_map(g, h->d, c->d.slab_bits, c->d.slab_shift, tmp.ptr, tmp_bytes, (uint32_t *)h->b_refresh_map.ptr, h->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(h->stream);
+    tmp.release();
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); // (clear the sticky allocation error: the handle stays usable with its old values)
+        h->b_refresh_map.release();
+        return fail_hip(e, "csr5hip_update_values: source map of the slab child");
+    }
+    h->refresh_map_valid = true;
+    return CSR5HIP_SUCCESS;
+}
+
+int csr5hip_update_values(csr5hip_handle h, const void *d_val_csr)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format != CSR5HIP_FORMAT_CSR && h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (h->g.nnz == 0)
+        return CSR5HIP_SUCCESS;
+    if (!d_val_csr)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const size_t bytes = (size_t)h->g.nnz * h->vsize();
+    {
+        const uintptr_t a = (uintptr_t)d_val_csr, v = (uintptr_t)h->d.val;
+        if (a < v + bytes && v < a + bytes) {
+            g_last_error = "csr5hip_update_values: d_val_csr overlaps the value array given to inputCSR (the handle keeps that array "
+                           "in its own order)";
+            return CSR5HIP_INVALID_ARGUMENT;
+        }
+    }
+    hipStream_t s = h->stream;
+    if (h->format == CSR5HIP_FORMAT_CSR) {
+        HIP_TRY(hipMemcpyAsync(h->d.val, d_val_csr, bytes, hipMemcpyDeviceToDevice, s));
+        return CSR5HIP_SUCCESS;
+    }
+    const csr5hip_handle c = h->slab_S > 0 ? h->slab_child : nullptr;
+    // the fp32 copy of a hot child's values is re-decided as build_slabs_impl decides it: one host synchronisation
+    const bool renarrow = c && c->hot_enabled && h->narrow_request && h->value_type == CSR5HIP_F64;
+    if (renarrow && stream_is_capturing(s)) {
+        g_last_error = "csr5hip_update_values: CSR5HIP_OPT_NARROW_VALUES re-checks the values on the host and cannot be captured";
+        return CSR5HIP_HIP_ERROR;
+    }
+    if (c && !h->refresh_map_valid) {
+        const int rc = build_refresh_map(h);
+        if (rc != CSR5HIP_SUCCESS)
+            return rc;
+    }
+    HIP_TRY(launch_refresh_values(h->g, h->d.tile_ptr, h->value_type, false, nullptr, d_val_csr, h->d.val, s));
+    if (!c)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_refresh_values(c->g, c->d.tile_ptr, c->value_type, c->hot_enabled, (const uint32_t *)h->b_refresh_map.ptr,
+                                  d_val_csr, c->d.val, s));
+    if (!renarrow)
+        return CSR5HIP_SUCCESS;
+    unsigned *flag = c->d.counters + 5;
+    unsigned inexact = 1;
+    HIP_TRY(launch_fp32_exact((const double *)c->d.val, (size_t)h->g.nnz, flag, s));
+    HIP_TRY(hipMemcpyAsync(&inexact, flag, sizeof(inexact), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    bool narrow = !inexact;
+    if (narrow) {
+        hipError_t e = h->b_val32.reserve((size_t)h->g.nnz * sizeof(float));
+        if (e == hipSuccess)
+            e = launch_narrow((const double *)c->d.val, (size_t)h->g.nnz, (float *)h->b_val32.ptr, c->g.tile_elems, c->g.p - 1, s);
+        if (e != hipSuccess) { // the copy is an optional accelerator: the fp64 values serve
+            (void)hipGetLastError();
+            set_last_error(std::string("csr5hip_update_values: fp32 copy of the values not built: ") + hipGetErrorString(e));
+            narrow = false;
+        }
+    }
+    if (narrow != h->values_narrowed) {
+        // another instantiation of the range kernel from here on: its LDS limit, and no graph recorded so far may be replayed
+        c->d.val32 = narrow ? (const float *)h->b_val32.ptr : nullptr;
+        h->values_narrowed = narrow;
+        h->drop_graphs();
+        HIP_TRY(prepare_spmv_hot(c->g, c->d, c->value_type, c->opt));
+    }
+    return CSR5HIP_SUCCESS;
+}
+
 int csr5hip_snapshot_x(csr5hip_handle h)
 {
     if (!h)
@@ -1869,7 +1978,8 @@ int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info)
     long long bytes = (long long)h->b_arena.cap;
     for (const Buffer *b : {&h->b_row_ptr2, &h->b_col2, &h->b_val2, &h->b_val32, &h->b_P, &h->b_rowidx, &h->b_base, &h->b_nonempty,
                             &h->b_hot_cols, &h->b_hot_count, &h->b_hot_tile0, &h->b_slab_off, &h->b_lead, &h->b_range_head, &h->b_slab_tmp,
-                            &h->b_col_lo, &h->b_col_hi, &h->b_cold_base, &h->b_cold_cols, &h->b_xperm, &h->b_col16, &h->b_col31})
+                            &h->b_col_lo, &h->b_col_hi, &h->b_cold_base, &h->b_cold_cols, &h->b_xperm, &h->b_col16, &h->b_col31,
+                            &h->b_refresh_map})
         bytes += (long long)b->cap;
     if (h->slab_child)
         bytes += (long long)h->slab_child->b_arena.cap;

@@ -16,7 +16,7 @@ namespace csr5 {
 //   1  the partial IS the row (row starts on the tile boundary and ends inside the tile): plain store.
 //   2  exchange handshake, ONE returning atomic per party: each party swaps the bit-inverted value
 //      into the slot (0 = empty, the memset state); whoever gets a non-zero word back is second, adds
-//      the two partials (a+b == b+a: bit-reproducible), stores y and re-arms the slot.  (The
+//      the two partials in tile order (bit-reproducible, NaN signs included), stores y and re-arms the slot.  (The
 //      all-ones NaN payload, whose inverse would read as "empty", is published as the default quiet NaN.)
 //   >2 rows spanning several tiles: every party parks its partial in its OWN word (leading partial of
 //      tile t -> calibrator[t], closing partial of tile h-1 -> acc[h]) with a write-through agent-scope
@@ -100,7 +100,18 @@ __device__ __forceinline__ void carry_arrive(VT *acc, uint32_t *cnt, VT *calibra
         const bits_t mine = ~vb;
         const bits_t other = __hip_atomic_exchange(s, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (other != 0) {
-            *row_y = v + __builtin_bit_cast(VT, (bits_t)~other);
+            // The two partials are added IN TILE ORDER, whoever arrives second.  For numbers a + b == b + a; for two NaNs the
+            // sum takes sign and payload from one operand, and with `v + other` that was the arrival order: y differed from run
+            // to run in the sign bit of a NaN.  The earlier party is the closing partial of tile slot-1 or, where the row starts
+            // on the boundary, the leading partial of tile `slot` itself.
+            const VT o = __builtin_bit_cast(VT, (bits_t)~other);
+            const bool mine_first = is_closing || (my_tile == slot && !((meta_x >> 27) & 1u));
+            const VT w = __builtin_bit_cast(VT, vb); // (what the other party would have read of this one)
+            VT lo = mine_first ? w : o, hi = mine_first ? o : w;
+            // (opaque to the optimiser: an fadd is commutative to the compiler, which folds (c ? w : o) + (c ? o : w) back
+            //  into w + o)
+            asm volatile("" : "+v"(lo), "+v"(hi));
+            *row_y = lo + hi;
             __hip_atomic_store(s, (bits_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     } else {

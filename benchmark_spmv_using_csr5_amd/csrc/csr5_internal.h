@@ -156,6 +156,17 @@ hipError_t launch_slab_combine(int m, int tail_start, int zero_empty, int S, int
                                const unsigned char *rowidx, const uint32_t *nonempty, const void *P, int segments, void *y,
                                hipStream_t s);
 
+// ---- value refresh (csr5_refresh.hip): csr5hip_update_values ----
+// out <- the values `in` (CSR order of the matrix g describes, or -- src != nullptr -- element j = in[src[j]]) in the storage order of a
+// converted value array: pieces = false the sigma x 64 transposition of launch_transpose (tile_ptr decides which tiles move), pieces =
+// true the lane-major 16-byte pieces of launch_transpose_values on every tile 0 .. p-2.  Out of place: in and out do not overlap.
+hipError_t launch_refresh_values(const Geometry &g, const uint32_t *tile_ptr, int value_type, bool pieces, const uint32_t *src,
+                                 const void *in, void *out, hipStream_t s);
+// source map of a slab child: src[q] = CSR rank in the parent (g, d: CSR5 form) of the child's q-th element in CSR order
+hipError_t refresh_map_tmp_bytes(int nnz, int bits, size_t *bytes);
+hipError_t refresh_build_map(const Geometry &g, const DeviceArrays &d, int bits, int shift, void *tmp, size_t tmp_bytes,
+                             uint32_t *src, hipStream_t s);
+
 // ---- SpMV (csr5_spmv.hip) ----
 struct SpmvOptions {
     int mode;        // CSR5HIP_OPT_SPMV_MODE

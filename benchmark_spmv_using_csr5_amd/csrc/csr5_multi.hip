@@ -134,6 +134,9 @@ struct csr5hip_multi_s {
     int G = 0, m = 0, n = 0, nnz = 0, value_type = CSR5HIP_F64;
     int row_weight = CSR5HIP_MULTI_DEFAULT_ROW_WEIGHT;
     std::vector<int> dev, cut, shard_nnz;
+    std::vector<int> nnz_lo;        // first non-zero of every shard in the whole matrix' CSR order
+    std::vector<void *> val_stage;  // update_values: landing buffer of a shard that does not live on devices[0] (first use)
+    bool has_matrix = false;        // input_csr completed
     std::vector<csr5hip_handle> h;
     std::vector<hipStream_t> stream;
     std::vector<void *> row_ptr, col, val, x, y;
@@ -179,6 +182,7 @@ int csr5hip_multi_create(csr5hip_multi *out, const int *devices, int G, int m, i
     mh->x_owned.assign(G, 0);
     mh->ev0.assign(G, nullptr), mh->ev1.assign(G, nullptr);
     mh->cut.assign(G + 1, 0), mh->shard_nnz.assign(G, 0);
+    mh->nnz_lo.assign(G, 0), mh->val_stage.assign(G, nullptr);
     DeviceGuard restore_device;
     for (int g = 0; g < G; g++) {
         hipError_t e = hipSetDevice(mh->dev[g]);
@@ -206,7 +210,7 @@ int csr5hip_multi_free(csr5hip_multi mh)
         (void)hipSetDevice(mh->dev[g]);
         if (mh->h[g])
             (void)csr5hip_free(mh->h[g]);
-        for (void *p : {mh->row_ptr[g], mh->col[g], mh->val[g], mh->y[g]})
+        for (void *p : {mh->row_ptr[g], mh->col[g], mh->val[g], mh->y[g], mh->val_stage[g]})
             if (p)
                 (void)hipFree(p);
         if (mh->x[g] && mh->x_owned[g])
@@ -226,6 +230,7 @@ int csr5hip_multi_input_csr(csr5hip_multi mh, int nnz, const int32_t *d_row_ptr,
     if (!mh || nnz < 0 || !d_row_ptr || (nnz > 0 && (!d_col_idx || !d_val)))
         return CSR5HIP_INVALID_ARGUMENT;
     mh->nnz = nnz;
+    mh->has_matrix = false;
     const int G = mh->G;
     // row cuts on device 0, where the matrix lies
     MHIP(hipSetDevice(mh->dev[0]));
@@ -246,12 +251,13 @@ int csr5hip_multi_input_csr(csr5hip_multi mh, int nnz, const int32_t *d_row_ptr,
         mh->cut[g] = cut[g];
         const int mg = cut[g + 1] - cut[g], nz = ptr_at[g + 1] - ptr_at[g];
         mh->shard_nnz[g] = nz;
+        mh->nnz_lo[g] = ptr_at[g];
         MHIP(hipSetDevice(mh->dev[g]));
         if (mh->h[g]) {
             (void)csr5hip_free(mh->h[g]);
             mh->h[g] = nullptr;
         }
-        for (void **p : {&mh->row_ptr[g], &mh->col[g], &mh->val[g], &mh->y[g]})
+        for (void **p : {&mh->row_ptr[g], &mh->col[g], &mh->val[g], &mh->y[g], &mh->val_stage[g]})
             if (*p) {
                 (void)hipFree(*p);
                 *p = nullptr;
@@ -285,6 +291,35 @@ int csr5hip_multi_input_csr(csr5hip_multi mh, int nnz, const int32_t *d_row_ptr,
         MHIP(hipStreamSynchronize(mh->stream[g]));
     }
     MHIP(hipSetDevice(mh->dev[0]));
+    mh->has_matrix = true;
+    return CSR5HIP_SUCCESS;
+}
+
+// A shard is a contiguous row block, hence a contiguous slice of the whole matrix' CSR-ordered values.  Shards on devices[0] read
+// their slice where it lies; a shard elsewhere receives it by a peer copy into a staging buffer of its own, on its own stream,
+// in front of its csr5hip_update_values.
+int csr5hip_multi_update_values(csr5hip_multi mh, const void *d_val_csr)
+{
+    DeviceGuard restore_device;
+    if (!mh || (mh->nnz > 0 && !d_val_csr))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (!mh->has_matrix)
+        return CSR5HIP_UNKOWN_FORMAT;
+    const size_t vs = mh->vsize();
+    for (int g = 0; g < mh->G; g++) {
+        const size_t nz = (size_t)mh->shard_nnz[g];
+        if (!nz)
+            continue;
+        MHIP(hipSetDevice(mh->dev[g]));
+        const void *slice = (const char *)d_val_csr + (size_t)mh->nnz_lo[g] * vs;
+        if (mh->dev[g] != mh->dev[0]) {
+            if (!mh->val_stage[g])
+                MHIP(hipMalloc(&mh->val_stage[g], nz * vs));
+            MHIP(hipMemcpyPeerAsync(mh->val_stage[g], mh->dev[g], slice, mh->dev[0], nz * vs, mh->stream[g]));
+            slice = mh->val_stage[g];
+        }
+        MRC(csr5hip_update_values(mh->h[g], slice));
+    }
     return CSR5HIP_SUCCESS;
 }
 

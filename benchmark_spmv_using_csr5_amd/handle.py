@@ -59,6 +59,7 @@ class anonymouslibHandle:
             raise RuntimeError(f"csr5hip_create -> {err}")
         self._keep = {}  # borrowed tensors, kept alive while the handle points at them
         self._m, self._n = int(m), int(n)
+        self._nnz = None  # known after inputCSR
         if stream is not None:
             self.setStream(stream)
 
@@ -68,6 +69,7 @@ class anonymouslibHandle:
 
     def inputCSR(self, nnz: int, csr_row_pointer, csr_column_index, csr_value) -> int:
         self._keep.update(row_ptr=csr_row_pointer, col=csr_column_index, val=csr_value)
+        self._nnz = int(nnz)
         return self._lib.csr5hip_input_csr(self._h, int(nnz), _ptr(csr_row_pointer),
                                            _ptr(csr_column_index), _ptr(csr_value))
 
@@ -120,6 +122,33 @@ class anonymouslibHandle:
     def spmm_ptr(self, X, ldx: int, k: int, Y, ldy: int) -> int:
         """csr5hip_spmm on raw device pointers (or tensors): X with leading dimension ldx, Y with ldy"""
         return self._lib.csr5hip_spmm(self._h, _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy))
+
+    def updateValues(self, val) -> int:
+        """New numerical values under the same pattern, without a new conversion (csr5hip.h csr5hip_update_values): ``val`` is a
+        contiguous 1-D GPU tensor of the handle's dtype with nnz elements in CSR order -- the order ``inputCSR``'s value tensor
+        had -- and must not share storage with that tensor (the handle keeps it in its own order).  Asynchronous on the
+        handle's stream; ``val`` is only read.  Anything else raises ValueError before the library is called."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        if not hasattr(val, "data_ptr") or not hasattr(val, "is_contiguous"):
+            raise ValueError("updateValues: val must be a torch tensor")
+        if self._nnz is None:
+            raise ValueError("updateValues: call inputCSR first")
+        if str(val.dtype) != dt:
+            raise ValueError(f"updateValues: val has dtype {val.dtype}, the handle holds {dt}")
+        if val.dim() != 1 or val.shape[0] != self._nnz:
+            raise ValueError(f"updateValues: val must have shape ({self._nnz},), not {tuple(val.shape)}")
+        if not val.is_contiguous():
+            raise ValueError(f"updateValues: val must be contiguous, not stride {val.stride()}")
+        mine = self._keep.get("val")
+        if hasattr(mine, "untyped_storage") and val.untyped_storage().data_ptr() == mine.untyped_storage().data_ptr():
+            raise ValueError("updateValues: val shares storage with the tensor given to inputCSR (aliased)")
+        if val.device.type != "cuda":
+            raise ValueError(f"updateValues: val must live on the GPU, not {val.device}")
+        return self.updateValues_ptr(val)
+
+    def updateValues_ptr(self, val) -> int:
+        """csr5hip_update_values on a raw device pointer (or tensor)"""
+        return self._lib.csr5hip_update_values(self._h, _ptr(val))
 
     # -- additions (documented in include/csr5hip.h) ---------------------------------------------
     def spmv_repeat(self, alpha, y, count: int) -> int:
@@ -271,7 +300,7 @@ class anonymouslibHandle:
             raise RuntimeError(f"csr5hip_load -> {err}: {_capi.last_error()}")
         self = cls.__new__(cls)
         self._lib, self._h, self._vt, self._keep = lib, h, int(raw.value_type), {}
-        self._m, self._n = int(raw.m), int(raw.n)
+        self._m, self._n, self._nnz = int(raw.m), int(raw.n), int(raw.nnz)
         self.arrays = DeviceCsr(raw)
         return self
 
@@ -331,6 +360,12 @@ class MultiGpuHandle:
     def setX(self, x) -> int:
         self._keep["x"] = x
         return self._lib.csr5hip_multi_set_x(self._h, _ptr(x))
+
+    def updateValues(self, val) -> int:
+        """the whole matrix' nnz values in CSR order on devices[0]; every shard takes its slice (csr5hip_multi_update_values).
+        Enqueued on the shards' streams: keep ``val`` unchanged until ``synchronize()``."""
+        self._keep["val"] = val
+        return self._lib.csr5hip_multi_update_values(self._h, _ptr(val))
 
     def spmv(self, alpha=1.0) -> int:
         return self._lib.csr5hip_multi_spmv(self._h, float(alpha))

@@ -138,6 +138,9 @@ public:
     {
         return _h ? csr5hip_spmm(_h, (const void *)X, ldx, k, (void *)Y, ldy) : _err;
     }
+    // extension: new values (nnz of them, CSR order, device pointer, not the array given to inputCSR) under the same pattern,
+    // without a new conversion (csr5hip.h csr5hip_update_values)
+    int updateValues(const ANONYMOUSLIB_VT *val) { return _h ? csr5hip_update_values(_h, (const void *)val) : _err; }
     int autotuneSigma(ANONYMOUSLIB_VT *y, int *sigma = 0, double *us = 0)
     {
         return _h ? csr5hip_autotune_sigma(_h, (void *)y, sigma, us) : _err;
@@ -191,6 +194,7 @@ public:
         return err;
     }
     int setX(ANONYMOUSLIB_VT *x) { return _h ? csr5hip_multi_set_x(_h, x) : _err; }
+    int updateValues(const ANONYMOUSLIB_VT *val) { return _h ? csr5hip_multi_update_values(_h, (const void *)val) : _err; }
     int spmv(const ANONYMOUSLIB_VT alpha) { return _h ? csr5hip_multi_spmv(_h, (double)alpha) : _err; }
     int spmv_repeat(const ANONYMOUSLIB_VT alpha, int count) { return _h ? csr5hip_multi_spmv_repeat(_h, (double)alpha, count) : _err; }
     int synchronize() { return _h ? csr5hip_multi_synchronize(_h) : _err; }

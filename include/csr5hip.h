@@ -221,6 +221,28 @@ int csr5hip_spmv(csr5hip_handle h, double alpha, void *d_y);
  * Returns CSR5HIP_INVALID_ARGUMENT for k < 0, ldx < k, ldy < k or null pointers with k > 0, CSR5HIP_UNSUPPORTED_CSR_SPMV
  * in CSR format, CSR5HIP_UNKOWN_FORMAT before inputCSR. */
 int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy);
+/* Extension (not in the reference): replace the matrix' numerical values, keep its pattern and everything derived from it.
+ * d_val_csr: nnz values of the handle's value type in CSR order (the order inputCSR's value array had), device pointer,
+ * read only, not retained.  It must not overlap the array given to inputCSR.
+ * CSR5 format: every later spmv, spmm, spmv_repeat, save and asCSR behaves exactly as if the handle had been built by inputCSR
+ * with the new values, the same options and the same sigma, then asCSR5(): bit for bit the same y on every path, the same
+ * tile-ordered value array, and asCSR() / destroy() hand the new values back in CSR order.  The conversion is NOT repeated: only
+ * the value arrays are rewritten (the handle's own, and with column slabs the stacked matrix' copy and its fp32 image).  The x
+ * snapshot (CSR5HIP_OPT_X_SNAPSHOT), the hot table, the permuted x, every column structure, every option and csr5hip_info stay as
+ * they are; device_bytes grows only by the helper below.
+ * CSR format: a device-to-device copy into the borrowed value array (caller code need not know the format).
+ * Asynchronous on the handle's stream: ordered after earlier spmv() calls and before later ones; d_val_csr must stay valid and
+ * unchanged until the work has run.  With column slabs the FIRST call after a conversion allocates and builds a pattern-only
+ * helper (4 bytes per non-zero: where every element of the stacked matrix comes from; one host synchronisation; counted in
+ * device_bytes; released with the slab structure); later calls only enqueue work, so update_values + spmv can be captured in a
+ * caller's graph on one stream.  One exception: a hot-table handle with CSR5HIP_OPT_NARROW_VALUES = 1 re-checks on every call
+ * that each new value is an exact fp32 number, which takes one host synchronisation (such a call cannot be captured);
+ * csr5hip_info.slab_values_narrowed reports the outcome.  When that outcome changes the library drops its own graphs
+ * (spmv_repeat / spmv_rotate re-record), and a graph the CALLER captured from this handle must be captured again.
+ * Returns CSR5HIP_INVALID_ARGUMENT for a null handle, a null pointer with nnz > 0 or a pointer that overlaps the handle's own
+ * value array; CSR5HIP_UNKOWN_FORMAT before inputCSR; CSR5HIP_HIP_ERROR (see csr5hip_last_error) when the helper cannot be
+ * allocated or the call cannot be captured -- the handle is then unchanged and still usable.  nnz = 0 is a successful no-op. */
+int csr5hip_update_values(csr5hip_handle h, const void *d_val_csr);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -379,6 +401,13 @@ int csr5hip_multi_as_csr5(csr5hip_multi mh);
 /* setX: d_x on devices[0], n values, borrowed by the shards that live there; ONE broadcast to the other devices, each shard's
  * permuted copy of x (hot-table path) taken right behind it.  Call again after changing x's contents. */
 int csr5hip_multi_set_x(csr5hip_multi mh, const void *d_x);
+/* csr5hip_update_values for the whole matrix.  d_val_csr: the whole matrix' nnz values in CSR order on devices[0]
+ * (the order input_csr's value array had); read only, not retained, must stay valid and unchanged until
+ * csr5hip_multi_synchronize.  Every shard takes its contiguous slice: shards on devices[0] read it in place, a shard on
+ * another device receives it by a peer copy into a staging buffer it owns (allocated on first use), then updates on its own
+ * stream.  Legal only after csr5hip_multi_input_csr (CSR5HIP_UNKOWN_FORMAT before); enqueues and returns like
+ * csr5hip_multi_spmv.  The shards' streams do not wait for the stream that wrote d_val_csr: synchronise it first. */
+int csr5hip_multi_update_values(csr5hip_multi mh, const void *d_val_csr);
 /* spmv on every shard, enqueued on the shards' streams (returns without waiting) */
 int csr5hip_multi_spmv(csr5hip_multi mh, double alpha);
 int csr5hip_multi_spmv_repeat(csr5hip_multi mh, double alpha, int count);
