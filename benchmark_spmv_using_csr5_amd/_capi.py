@@ -69,6 +69,9 @@ class Csr5Info(C.Structure):
         ("flagged_columns", C.c_int),
         ("lds_y", C.c_int),
         ("stream_nt", C.c_int),
+        ("transpose_built", C.c_int), ("t_transpose_build_ms", C.c_double),
+        ("t_sigma", C.c_int), ("t_p", C.c_int), ("t_tail_partition_start", C.c_int),
+        ("t_column_slabs", C.c_int), ("t_slab_hot", C.c_int), ("t_x_window_active", C.c_int),
     ]
 
 
@@ -117,6 +120,9 @@ SYMBOLS = [
     ("csr5hip_spmv", C.c_int, [_H, C.c_double, C.c_void_p]),
     ("csr5hip_spmm", C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     ("csr5hip_update_values", C.c_int, [_H, C.c_void_p]),
+    ("csr5hip_build_transpose", C.c_int, [_H]),
+    ("csr5hip_spmv_t", C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    ("csr5hip_spmm_t", C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     ("csr5hip_spmv_repeat", C.c_int, [_H, C.c_double, C.c_void_p, C.c_int]),
     ("csr5hip_spmv_rotate", C.c_int, [C.POINTER(_H), C.POINTER(C.c_void_p), C.c_int, C.c_double, C.c_int]),
     ("csr5hip_snapshot_x", C.c_int, [_H]),

@@ -164,6 +164,15 @@ struct csr5hip_handle_s {
     // a conversion (it depends on the column indices only) and released with the slab structure
     Buffer b_refresh_map;
     bool refresh_map_valid = false;
+    // transposed companion (csr5hip_build_transpose, csr5_companion.hip): a library-owned CSR of A^T, converted as an ordinary
+    // handle of shape (n, m) on this handle's stream; released by asCSR / inputCSR / free
+    bool sigma_auto = true;     // the caller's last sigma request was AUTO (or none): re-resolved for the transposed shape
+    bool at_built = false;      // a companion exists (with nnz = 0: nothing is allocated and `at` stays null)
+    csr5hip_handle_s *at = nullptr;
+    Buffer b_at_row_ptr, b_at_col, b_at_val; // the CSR of A^T (col / val in tile order once `at` is converted)
+    Buffer b_at_map;            // source map: position in A^T's CSR -> position in A's CSR (4 bytes per non-zero)
+    Buffer b_at_stage;          // csr5hip_update_values: the new values in A^T's CSR order
+    double t_at_build = 0;      // device build + conversion, ms
 
     // csr5hip_spmv_rotate: one graph over several handles (cold-cache measurement protocol)
     hipGraphExec_t rotate_exec = nullptr;
@@ -258,11 +267,25 @@ int csr5hip_create(csr5hip_handle *out, int m, int n, int value_type)
 
 static void release_slabs(csr5hip_handle h);
 
+// the transposed companion and everything held for it (csr5hip_build_transpose)
+static void release_companion(csr5hip_handle h)
+{
+    if (h->at) {
+        csr5hip_free(h->at);
+        h->at = nullptr;
+    }
+    h->at_built = false;
+    h->t_at_build = 0;
+    for (Buffer *b : {&h->b_at_row_ptr, &h->b_at_col, &h->b_at_val, &h->b_at_map, &h->b_at_stage})
+        b->release();
+}
+
 int csr5hip_free(csr5hip_handle h)
 {
     if (!h)
         return CSR5HIP_INVALID_ARGUMENT;
     h->drop_graphs();
+    release_companion(h);
     release_slabs(h);
     h->b_arena.release();
     h->b_col16.release();
@@ -283,6 +306,8 @@ int csr5hip_set_stream(csr5hip_handle h, void *hip_stream)
     h->stream = (hipStream_t)hip_stream;
     h->xperm_valid = false; // (snapshot mode: the copy was taken on the old stream; the new one takes its own, in order)
     h->drop_graphs();
+    if (h->at) // (the companion lives on its parent's stream)
+        return csr5hip_set_stream(h->at, hip_stream);
     return CSR5HIP_SUCCESS;
 }
 
@@ -298,6 +323,7 @@ int csr5hip_input_csr(csr5hip_handle h, int nnz, int32_t *d_row_ptr, int32_t *d_
 {
     if (!h || nnz < 0)
         return CSR5HIP_INVALID_ARGUMENT;
+    release_companion(h); // (it belonged to the matrix that is being replaced)
     h->format = CSR5HIP_FORMAT_CSR;
     h->g.nnz = nnz;
     h->d.row_ptr = d_row_ptr;
@@ -343,11 +369,13 @@ int csr5hip_set_sigma(csr5hip_handle h, int sigma)
 {
     if (!h)
         return CSR5HIP_INVALID_ARGUMENT;
-    if (sigma == CSR5HIP_AUTO_TUNED_SIGMA)
+    const bool is_auto = sigma == CSR5HIP_AUTO_TUNED_SIGMA;
+    if (is_auto)
         sigma = csr5hip_auto_sigma(h->g.m, h->g.nnz, h->value_type);
     if (sigma < CSR5HIP_MIN_SIGMA || sigma > CSR5HIP_MAX_SIGMA)
         return CSR5HIP_INVALID_ARGUMENT;
     h->sigma_request = sigma;
+    h->sigma_auto = is_auto;
     return CSR5HIP_SUCCESS;
 }
 
@@ -363,10 +391,21 @@ static int prepare_plain(csr5hip_handle h)
     return rc != CSR5HIP_SUCCESS ? rc : prepare_col31(h);
 }
 
+static int set_option_impl(csr5hip_handle h, int option, int value);
+
+// A transposed companion carries every option of its parent except CSR5HIP_OPT_X_SNAPSHOT (spmv_t takes x per call and reads it live)
 int csr5hip_set_option(csr5hip_handle h, int option, int value)
 {
     if (!h)
         return CSR5HIP_INVALID_ARGUMENT;
+    const int rc = set_option_impl(h, option, value);
+    if (rc != CSR5HIP_SUCCESS || !h->at || option == CSR5HIP_OPT_X_SNAPSHOT)
+        return rc;
+    return set_option_impl(h->at, option, value);
+}
+
+static int set_option_impl(csr5hip_handle h, int option, int value)
+{
     switch (option) {
     case CSR5HIP_OPT_SPMV_MODE:
         if (value != 0 && value != 1)
@@ -1479,6 +1518,7 @@ int csr5hip_load(const char *path, csr5hip_handle *out, csr5hip_csr *arrays)
         return fail_with(CSR5HIP_INVALID_ARGUMENT, "truncated file");
     csr5hip_input_csr(h, hd.nnz, arrays->d_row_ptr, arrays->d_col_idx, arrays->d_val);
     h->sigma_request = hd.sigma;
+    h->sigma_auto = false;
     rc = derive_geometry(h, hd.sigma);
     if (rc == CSR5HIP_SUCCESS)
         rc = reserve_aux(h);
@@ -1568,6 +1608,7 @@ int csr5hip_as_csr(csr5hip_handle h)
     HIP_TRY(launch_transpose(h->g, h->d, h->value_type, false, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->b_spmm.release(); // (the SpMM workspace is sized by the converted matrix: released with it)
+    release_companion(h); // (so is the transposed companion)
     // the aux buffers stay cached in the handle (capacity only grows) until csr5hip_free
     h->format = CSR5HIP_FORMAT_CSR;
     return CSR5HIP_SUCCESS;
@@ -1649,7 +1690,31 @@ static int build_refresh_map(csr5hip_handle h)
     return CSR5HIP_SUCCESS;
 }
 
+static int update_values_self(csr5hip_handle h, const void *d_val_csr);
+
+// With a transposed companion the same call gives it the new values too: gathered through the source map into the staging buffer
+// (A^T's CSR order), then the companion's own refresh, on the same stream behind the parent's.  Whatever cannot be enqueued -- the
+// source map of the companion's slab child, built by its first update -- is done BEFORE anything is changed.
 int csr5hip_update_values(csr5hip_handle h, const void *d_val_csr)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    csr5hip_handle t = h->format == CSR5HIP_FORMAT_CSR5 ? h->at : nullptr;
+    if (!t || !d_val_csr)
+        return update_values_self(h, d_val_csr);
+    if (t->slab_S > 0 && !t->refresh_map_valid) {
+        const int rc = build_refresh_map(t);
+        if (rc != CSR5HIP_SUCCESS)
+            return rc;
+    }
+    int rc = update_values_self(h, d_val_csr);
+    if (rc != CSR5HIP_SUCCESS)
+        return rc;
+    HIP_TRY(companion_gather(h->g.nnz, (int)h->vsize(), (const uint32_t *)h->b_at_map.ptr, d_val_csr, h->b_at_stage.ptr, h->stream));
+    return update_values_self(t, h->b_at_stage.ptr);
+}
+
+static int update_values_self(csr5hip_handle h, const void *d_val_csr)
 {
     if (!h)
         return CSR5HIP_INVALID_ARGUMENT;
@@ -1714,6 +1779,152 @@ int csr5hip_update_values(csr5hip_handle h, const void *d_val_csr)
         h->values_narrowed = narrow;
         h->drop_graphs();
         HIP_TRY(prepare_spmv_hot(c->g, c->d, c->value_type, c->opt));
+    }
+    return CSR5HIP_SUCCESS;
+}
+
+// ---- transposed companion (csr5_companion.hip) --------------------------------------------------------------------------------
+// The CSR of A^T and its source map from the parent's tile-ordered arrays, then an ordinary conversion of a handle of shape (n, m)
+// that carries the parent's value type, stream, sigma request and options.  Nothing of the parent is modified.
+static int build_companion(csr5hip_handle h)
+{
+    const Geometry &g = h->g;
+    hipStream_t s = h->stream;
+    const size_t vs = h->vsize();
+    size_t tmp_bytes = 0;
+    Buffer tmp;
+    hipError_t e = companion_tmp_bytes(g.n, g.nnz, &tmp_bytes);
+    if (e == hipSuccess)
+        e = h->b_at_row_ptr.reserve(((size_t)g.n + 1) * 4);
+    if (e == hipSuccess)
+        e = h->b_at_col.reserve((size_t)g.nnz * 4);
+    if (e == hipSuccess)
+        e = h->b_at_val.reserve((size_t)g.nnz * vs);
+    if (e == hipSuccess)
+        e = h->b_at_map.reserve((size_t)g.nnz * 4);
+    if (e == hipSuccess)
+        e = h->b_at_stage.reserve((size_t)g.nnz * vs);
+    if (e == hipSuccess)
+        e = tmp.reserve(tmp_bytes);
+    if (e == hipSuccess)
+        e = companion_build(g, h->d, (int)vs, tmp.ptr, tmp_bytes, (int32_t *)h->b_at_row_ptr.ptr, (int32_t *)h->b_at_col.ptr,
+                            h->b_at_val.ptr, (uint32_t *)h->b_at_map.ptr, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    tmp.release();
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); // (clear the sticky allocation error: the parent stays usable)
+        return fail_hip(e, "csr5hip_build_transpose: CSR of the transposed matrix");
+    }
+    csr5hip_handle t = new csr5hip_handle_s();
+    h->at = t;
+    t->g.m = g.n;
+    t->g.n = g.m;
+    t->value_type = h->value_type;
+    t->stream = s;
+    t->opt.mode = h->opt.mode;
+    t->opt.xcd_remap = h->opt.xcd_remap;
+    t->nt_request = h->nt_request;
+    t->ldsy_request = h->ldsy_request;
+    t->xwin_request = h->xwin_request;
+    t->defer_request = h->defer_request;
+    t->col16_request = h->col16_request;
+    t->col31_request = h->col31_request;
+    t->slab_request = h->slab_request;
+    t->slab_shift = h->slab_shift;
+    t->slab_mem_mib = h->slab_mem_mib;
+    t->hot_request = h->hot_request;
+    t->narrow_request = h->narrow_request;
+    t->zero_empty = h->zero_empty;
+    t->x_snapshot = 0; // spmv_t takes x per call: always read live
+    int rc = csr5hip_input_csr(t, g.nnz, (int32_t *)h->b_at_row_ptr.ptr, (int32_t *)h->b_at_col.ptr, h->b_at_val.ptr);
+    t->sigma_auto = h->sigma_auto;
+    t->sigma_request = h->sigma_auto || h->sigma_request < CSR5HIP_MIN_SIGMA ? csr5hip_auto_sigma(t->g.m, g.nnz, t->value_type)
+                                                                              : h->sigma_request;
+    if (rc == CSR5HIP_SUCCESS)
+        rc = csr5hip_as_csr5(t);
+    return rc;
+}
+
+int csr5hip_build_transpose(csr5hip_handle h)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (h->at_built)
+        return CSR5HIP_SUCCESS;
+    if (h->g.nnz == 0) { // nothing to hold: spmv_t applies the empty-row contract to all n rows
+        h->at_built = true;
+        return CSR5HIP_SUCCESS;
+    }
+    if (stream_is_capturing(h->stream)) {
+        g_last_error = "csr5hip_build_transpose allocates and synchronises and cannot be captured: call it outside the capture";
+        return CSR5HIP_HIP_ERROR;
+    }
+    const double t0 = now_ms();
+    const int rc = build_companion(h);
+    if (rc != CSR5HIP_SUCCESS) {
+        const std::string why = g_last_error;
+        (void)hipGetLastError();
+        release_companion(h);
+        g_last_error = why;
+        return rc;
+    }
+    h->at_built = true;
+    h->t_at_build = now_ms() - t0;
+    return CSR5HIP_SUCCESS;
+}
+
+static int companion_ready(csr5hip_handle h, const char *who)
+{
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (!h->at_built) {
+        g_last_error = std::string(who) + ": no transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    return CSR5HIP_SUCCESS;
+}
+
+// y = A^T x: one spmv() of the companion with the caller's x, on whatever path its conversion selected
+int csr5hip_spmv_t(csr5hip_handle h, const void *d_x, void *d_y)
+{
+    if (!h || !d_x || !d_y)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int rc = companion_ready(h, "csr5hip_spmv_t");
+    if (rc != CSR5HIP_SUCCESS)
+        return rc;
+    csr5hip_handle t = h->at;
+    if (!t) { // nnz = 0: every row of A^T is an empty row in front of the tail
+        if (h->zero_empty && h->g.n > 0)
+            HIP_TRY(hipMemsetAsync(d_y, 0, (size_t)h->g.n * h->vsize(), h->stream));
+        return CSR5HIP_SUCCESS;
+    }
+    t->x = d_x; // (the companion records no graphs of its own and keeps no snapshot: nothing to invalidate)
+    HIP_TRY(enqueue_spmv(t, d_y, t->stream, false));
+    return CSR5HIP_SUCCESS;
+}
+
+// Y = A^T X: csr5hip_spmm of the companion
+int csr5hip_spmm_t(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy)
+{
+    if (!h || k < 0 || ldx < k || ldy < k || (k > 0 && (!d_X || !d_Y)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int rc = companion_ready(h, "csr5hip_spmm_t");
+    if (rc != CSR5HIP_SUCCESS)
+        return rc;
+    if (h->at)
+        return csr5hip_spmm(h->at, d_X, ldx, k, d_Y, ldy);
+    if (k > 0) { // nnz = 0
+        Geometry gt{};
+        gt.m = h->g.n;
+        gt.n = h->g.m;
+        HIP_TRY(launch_spmm(gt, DeviceArrays{}, h->value_type, d_X, ldx, k, d_Y, ldy, nullptr, h->zero_empty, 0, h->stream));
     }
     return CSR5HIP_SUCCESS;
 }
@@ -1872,6 +2083,7 @@ int csr5hip_autotune_sigma(csr5hip_handle h, void *d_y, int *best_sigma, double 
         if ((long long)OMEGA * sigma > (long long)h->g.nnz && sigma != 4)
             continue; // fewer non-zeros than one tile: nothing to choose
         h->sigma_request = sigma;
+        h->sigma_auto = false;
         rc = csr5hip_as_csr5(h);
         if (rc != CSR5HIP_SUCCESS)
             return rc;
@@ -1914,6 +2126,7 @@ int csr5hip_autotune_sigma(csr5hip_handle h, void *d_y, int *best_sigma, double 
         if (rc != CSR5HIP_SUCCESS)
             return rc;
     }
+    h->sigma_auto = !best;
     if (!best)
         best = csr5hip_auto_sigma(h->g.m, h->g.nnz, h->value_type);
     h->sigma_request = best;
@@ -1983,6 +2196,24 @@ int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info)
         bytes += (long long)b->cap;
     if (h->slab_child)
         bytes += (long long)h->slab_child->b_arena.cap;
+    info->transpose_built = h->at_built ? 1 : 0;
+    info->t_transpose_build_ms = h->t_at_build;
+    if (h->at) {
+        csr5hip_info ti;
+        csr5hip_get_info(h->at, &ti);
+        info->t_sigma = ti.sigma;
+        info->t_p = ti.p;
+        info->t_tail_partition_start = ti.tail_partition_start;
+        info->t_column_slabs = ti.column_slabs;
+        info->t_slab_hot = ti.slab_hot;
+        info->t_x_window_active = ti.x_window_active;
+        bytes += ti.device_bytes;
+        for (const Buffer *b : {&h->b_at_row_ptr, &h->b_at_col, &h->b_at_val, &h->b_at_map, &h->b_at_stage})
+            bytes += (long long)b->cap;
+    } else if (h->at_built) { // nnz = 0: what a handle of the empty n x m matrix reports
+        info->t_sigma = h->sigma_auto ? csr5hip_auto_sigma(h->g.n, 0, h->value_type) : h->sigma_request;
+        info->t_tail_partition_start = h->g.n;
+    }
     info->device_bytes = bytes;
     return CSR5HIP_SUCCESS;
 }

@@ -167,6 +167,15 @@ hipError_t refresh_map_tmp_bytes(int nnz, int bits, size_t *bytes);
 hipError_t refresh_build_map(const Geometry &g, const DeviceArrays &d, int bits, int shift, void *tmp, size_t tmp_bytes,
                              uint32_t *src, hipStream_t s);
 
+// ---- transposed companion (csr5_companion.hip): csr5hip_build_transpose ----
+// The CSR of A^T (row j = A's entries of column j in the order they have in A's CSR arrays) and its source map -- map[q] = position
+// in A's CSR of the q-th element of A^T's CSR -- from the parent (g, d: CSR5 form).  value_size 4 or 8; tmp from companion_tmp_bytes.
+hipError_t companion_tmp_bytes(int n, int nnz, size_t *bytes);
+hipError_t companion_build(const Geometry &g, const DeviceArrays &d, int value_size, void *tmp, size_t tmp_bytes,
+                           int32_t *row_ptr_t, int32_t *col_t, void *val_t, uint32_t *map, hipStream_t s);
+// out[q] = in[map[q]] for q < nnz: values in A's CSR order carried into A^T's
+hipError_t companion_gather(int nnz, int value_size, const uint32_t *map, const void *in, void *out, hipStream_t s);
+
 // ---- SpMV (csr5_spmv.hip) ----
 struct SpmvOptions {
     int mode;        // CSR5HIP_OPT_SPMV_MODE

@@ -96,32 +96,73 @@ class anonymouslibHandle:
         """Y = A * X for k dense vectors (csr5hip.h csr5hip_spmm): X (n, k) and Y (m, k) device tensors of the handle's
         dtype with stride(1) == 1; the leading dimensions are their stride(0).  Column c of Y equals a two-pass spmv() of
         X[:, c], bit for bit.  Wrong dtype, device, shape or inner stride raise ValueError before the library is called."""
+        return self.spmm_ptr(*self._spmm_args("spmm", X, self._n, Y, self._m))
+
+    def _spmm_args(self, who: str, X, x_rows: int, Y, y_rows: int):
+        """the checks of spmm / spmmT: (X, ldx, k, Y, ldy) for the C call, or ValueError"""
         dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        for name, t, rows in (("X", X, self._n), ("Y", Y, self._m)):
+        for name, t, rows in (("X", X, x_rows), ("Y", Y, y_rows)):
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
-                raise ValueError(f"spmm: {name} must be a torch tensor")
+                raise ValueError(f"{who}: {name} must be a torch tensor")
             if str(t.dtype) != dt:
-                raise ValueError(f"spmm: {name} has dtype {t.dtype}, the handle holds {dt}")
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
             if t.dim() != 2 or t.shape[0] != rows:
-                raise ValueError(f"spmm: {name} must have shape ({rows}, k), not {tuple(t.shape)}")
+                raise ValueError(f"{who}: {name} must have shape ({rows}, k), not {tuple(t.shape)}")
             if t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError(f"spmm: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+                raise ValueError(f"{who}: {name} must be row-major with stride(1) == 1, not {t.stride()}")
             if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
-                raise ValueError(f"spmm: {name} rows overlap (stride(0) {t.stride(0)} < k = {t.shape[1]})")
+                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < k = {t.shape[1]})")
             if t.device.type != "cuda":
-                raise ValueError(f"spmm: {name} must live on the GPU, not {t.device}")
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
         if X.shape[1] != Y.shape[1]:
-            raise ValueError(f"spmm: X has {X.shape[1]} columns, Y {Y.shape[1]}")
+            raise ValueError(f"{who}: X has {X.shape[1]} columns, Y {Y.shape[1]}")
         if X.device != Y.device:
-            raise ValueError(f"spmm: X on {X.device}, Y on {Y.device}")
+            raise ValueError(f"{who}: X on {X.device}, Y on {Y.device}")
         k = int(X.shape[1])
         ldx = max(int(X.stride(0)), k) if X.shape[0] > 1 else k
         ldy = max(int(Y.stride(0)), k) if Y.shape[0] > 1 else k
-        return self.spmm_ptr(X, ldx, k, Y, ldy)
+        return X, ldx, k, Y, ldy
 
     def spmm_ptr(self, X, ldx: int, k: int, Y, ldy: int) -> int:
         """csr5hip_spmm on raw device pointers (or tensors): X with leading dimension ldx, Y with ldy"""
         return self._lib.csr5hip_spmm(self._h, _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy))
+
+    # -- products with the transpose (csr5hip.h csr5hip_build_transpose) ---------------------------
+    def buildTranspose(self) -> int:
+        """Give the converted handle a transposed companion (a library-owned CSR5 form of A^T, built on the device, kept current by
+        ``updateValues``): once per conversion, allocates and synchronises.  ``spmvT`` / ``spmmT`` need it."""
+        return self._lib.csr5hip_build_transpose(self._h)
+
+    def spmvT(self, x, y) -> int:
+        """y = A^T x: x (m,) and y (n,) contiguous GPU tensors of the handle's dtype; the handle's own x (setX) is not involved.
+        Wrong dtype, device, shape or stride raise ValueError before the library is called."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        for name, t, rows in (("x", x, self._m), ("y", y, self._n)):
+            if not hasattr(t, "data_ptr") or not hasattr(t, "is_contiguous"):
+                raise ValueError(f"spmvT: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"spmvT: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 1 or t.shape[0] != rows:
+                raise ValueError(f"spmvT: {name} must have shape ({rows},), not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"spmvT: {name} must be contiguous, not stride {t.stride()}")
+            if t.device.type != "cuda":
+                raise ValueError(f"spmvT: {name} must live on the GPU, not {t.device}")
+        if x.device != y.device:
+            raise ValueError(f"spmvT: x on {x.device}, y on {y.device}")
+        return self.spmvT_ptr(x, y)
+
+    def spmvT_ptr(self, x, y) -> int:
+        """csr5hip_spmv_t on raw device pointers (or tensors)"""
+        return self._lib.csr5hip_spmv_t(self._h, _ptr(x), _ptr(y))
+
+    def spmmT(self, X, Y) -> int:
+        """Y = A^T X for k dense vectors: X (m, k), Y (n, k), otherwise as ``spmm``"""
+        return self.spmmT_ptr(*self._spmm_args("spmmT", X, self._m, Y, self._n))
+
+    def spmmT_ptr(self, X, ldx: int, k: int, Y, ldy: int) -> int:
+        """csr5hip_spmm_t on raw device pointers (or tensors): X with leading dimension ldx, Y with ldy"""
+        return self._lib.csr5hip_spmm_t(self._h, _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy))
 
     def updateValues(self, val) -> int:
         """New numerical values under the same pattern, without a new conversion (csr5hip.h csr5hip_update_values): ``val`` is a

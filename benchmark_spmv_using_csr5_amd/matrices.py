@@ -191,6 +191,22 @@ def example_matrix(seed: int = 7, dtype=np.float64) -> CsrMatrix:
     return csr_from_row_lengths(lengths, m, rng, band=0.0, name="example(synthetic)", dtype=dtype)
 
 
+def transpose_csr(mat: CsrMatrix, return_map: bool = False):
+    """The canonical transpose (csr5hip.h csr5hip_build_transpose): row j of the result holds ``mat``'s entries of column j in
+    ascending order of their position in ``mat``'s CSR arrays -- ascending row, repeated (row, column) pairs in the order they
+    have in ``mat`` -- i.e. a stable sort of the column array.  With ``return_map`` also the source map: ``map[q]`` = position
+    in ``mat``'s CSR arrays of the result's q-th entry, so that ``val_T == val[map]`` for any values of ``mat``'s pattern."""
+    nnz = mat.nnz
+    col = np.asarray(mat.col[:nnz], dtype=np.int64)
+    src = np.argsort(col, kind="stable")
+    rows = np.repeat(np.arange(mat.m, dtype=np.int64), np.diff(mat.row_ptr).astype(np.int64))
+    row_ptr = np.zeros(mat.n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(col, minlength=mat.n), out=row_ptr[1:])
+    out = CsrMatrix(mat.n, mat.m, row_ptr.astype(mat.row_ptr.dtype), rows[src].astype(mat.col.dtype),
+                    np.asarray(mat.val)[:nnz][src], f"{mat.name}^T")
+    return (out, src.astype(np.int64)) if return_map else out
+
+
 # ---------------------------------------------------------------------------------------------
 # Matrix Market ingest / writer (CSR5_avx2/main.cpp:135-275)
 # ---------------------------------------------------------------------------------------------

@@ -141,6 +141,14 @@ public:
     // extension: new values (nnz of them, CSR order, device pointer, not the array given to inputCSR) under the same pattern,
     // without a new conversion (csr5hip.h csr5hip_update_values)
     int updateValues(const ANONYMOUSLIB_VT *val) { return _h ? csr5hip_update_values(_h, (const void *)val) : _err; }
+    // extension: products with the transpose (csr5hip.h csr5hip_build_transpose).  buildTranspose() once per conversion (allocates,
+    // synchronises); then y = A^T x with x: m values, y: n values, and Y = A^T X with X: m x k, Y: n x k; device pointers
+    int buildTranspose() { return _h ? csr5hip_build_transpose(_h) : _err; }
+    int spmvT(const ANONYMOUSLIB_VT *x, ANONYMOUSLIB_VT *y) { return _h ? csr5hip_spmv_t(_h, (const void *)x, (void *)y) : _err; }
+    int spmmT(const ANONYMOUSLIB_VT *X, int ldx, int k, ANONYMOUSLIB_VT *Y, int ldy)
+    {
+        return _h ? csr5hip_spmm_t(_h, (const void *)X, ldx, k, (void *)Y, ldy) : _err;
+    }
     int autotuneSigma(ANONYMOUSLIB_VT *y, int *sigma = 0, double *us = 0)
     {
         return _h ? csr5hip_autotune_sigma(_h, (void *)y, sigma, us) : _err;

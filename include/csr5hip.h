@@ -184,6 +184,10 @@ typedef struct csr5hip_info {
     int flagged_columns;           /* 1 = the plain kernel streams column words with the row-start flag in bit 31 (CSR5HIP_OPT_FLAGGED_COLUMNS) */
     int lds_y;                     /* 1 = the plain kernel compacts y segments in LDS (CSR5HIP_OPT_LDS_Y and 64*sigma*sizeof(vT) <= 8 KiB) */
     int stream_nt;                 /* 1 = the plain fused kernel streams column_index / value with non-temporal loads (CSR5HIP_OPT_STREAM_NT) */
+    int transpose_built;           /* 1 = a transposed companion exists (csr5hip_build_transpose): spmv_t / spmm_t are legal        */
+    double t_transpose_build_ms;   /* time csr5hip_build_transpose took: device build of the CSR of A^T + its conversion            */
+    int t_sigma, t_p, t_tail_partition_start;          /* the companion's sigma, p, tail_partition_start ...                        */
+    int t_column_slabs, t_slab_hot, t_x_window_active; /* ... and the variant its spmv runs (column_slabs, slab_hot, x_window_active) */
 } csr5hip_info;
 
 /* anonymouslibHandle(m, n) -- anonymouslib_cuda.h:15.  Uses the current HIP device. */
@@ -243,6 +247,42 @@ int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, i
  * value array; CSR5HIP_UNKOWN_FORMAT before inputCSR; CSR5HIP_HIP_ERROR (see csr5hip_last_error) when the helper cannot be
  * allocated or the call cannot be captured -- the handle is then unchanged and still usable.  nnz = 0 is a successful no-op. */
 int csr5hip_update_values(csr5hip_handle h, const void *d_val_csr);
+/* Extension (not in the reference): products with the transpose, y = A^T x, on the converted handle.
+ * csr5hip_build_transpose gives a handle in CSR5 format a TRANSPOSED COMPANION: a library-owned CSR of A^T (n rows, m columns)
+ * built on the device from the handle's tile-ordered arrays, then converted to CSR5 as an ordinary internal handle on the same
+ * stream.  Row j of A^T holds A's entries of column j in ascending order of their position in A's CSR arrays (ascending row;
+ * repeated (row, column) pairs keep the order they have in A) -- what a stable sort of the CSR column array gives -- so every
+ * result equals, bit for bit, that of a handle the caller builds by hand from such a transposed CSR with the same value type,
+ * sigma request and options.  The companion carries the sigma request last made on this handle (AUTO is re-resolved for the
+ * transposed shape, csr5hip_auto_sigma(n, nnz, type)) and every csr5hip_set_option value of this handle, at build time and
+ * whenever one is set later, except CSR5HIP_OPT_X_SNAPSHOT (0: spmv_t reads its x live).  A column-slab structure that only
+ * the auto rule wanted and that does not fit CSR5HIP_OPT_SLAB_MEMORY_MIB falls back as on any handle.
+ * The call allocates and synchronises (not capturable: CSR5HIP_HIP_ERROR + csr5hip_last_error while the stream is capturing).
+ * A no-op when a companion exists; with nnz = 0 it succeeds and allocates nothing.  The handle's own arrays, results, graphs
+ * and csr5hip_info (apart from the fields below and device_bytes) are untouched.  If anything fails, everything allocated for
+ * the companion is released, the handle stays usable and the error is returned.
+ * Memory (csr5hip_info.device_bytes counts all of it): the CSR of A^T (nnz x (4 + sizeof value) + 4 (n + 1) bytes), its CSR5
+ * arrays and kernel tables, the source map (4 bytes per non-zero: position in A^T's CSR -> position in A's) and a staging
+ * buffer of nnz values for csr5hip_update_values.
+ * Lifetime: released by asCSR / destroy / free and inputCSR (csr5hip_autotune_sigma re-converts and so drops it); save / load
+ * do not carry it, a loaded handle can build one.  csr5hip_update_values on this handle also gives the companion the new
+ * values, on the same stream behind the handle's own update (with column slabs on the companion its first such call builds
+ * that structure's helper and synchronises once; later calls only enqueue).
+ * Returns CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format, CSR5HIP_UNKOWN_FORMAT before inputCSR.
+ * Single handles only: csr5hip_multi has no transposed product (A^T of a row block needs a sum across the shards). */
+int csr5hip_build_transpose(csr5hip_handle h);
+/* y = A^T x.  d_x: m values, d_y: n values, device pointers.  Asynchronous on the handle's stream, enqueue-only (capturable in
+ * a caller's graph on that stream).  The handle's own x (setX) is neither needed nor touched; no alpha.  Rows of y follow
+ * spmv()'s contract on the transposed matrix: every row of A^T that owns a non-zero and every row >=
+ * csr5hip_info.t_tail_partition_start is overwritten, other empty rows only with CSR5HIP_OPT_ZERO_EMPTY_ROWS.
+ * Returns CSR5HIP_INVALID_ARGUMENT for null pointers or when no companion exists (csr5hip_last_error: call
+ * csr5hip_build_transpose first -- it is never built lazily), CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format,
+ * CSR5HIP_UNKOWN_FORMAT before inputCSR. */
+int csr5hip_spmv_t(csr5hip_handle h, const void *d_x, void *d_y);
+/* Y = A^T X for k dense vectors: csr5hip_spmm's contract on the companion (X: m rows x k, ldx >= k; Y: n rows x k, ldy >= k;
+ * column c bit-identical to a two-pass spmv of the transposed matrix with x = X[:, c]); errors as csr5hip_spmm and
+ * csr5hip_spmv_t. */
+int csr5hip_spmm_t(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
