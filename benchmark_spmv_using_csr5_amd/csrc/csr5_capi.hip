@@ -1657,6 +1657,25 @@ int csr5hip_spmm(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, i
     return CSR5HIP_SUCCESS;
 }
 
+// out[e] = dot(U[row(e), :], V[col(e), :]) for every stored element, CSR order (csr5_sddmm.hip).  Runs on the handle's own tile
+// structure whatever path spmv() takes; reads only pattern-derived arrays; allocates nothing: enqueue-only from the first call.
+int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, int ldv, int k, void *d_out_csr)
+{
+    if (!h || k < 0 || ldu < k || ldv < k)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (nnz > 0 && ((k > 0 && (!d_U || !d_V)) || !d_out_csr))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (nnz == 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_sddmm(h->g, h->d, h->value_type, d_U, ldu, d_V, ldv, k, d_out_csr, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

@@ -238,6 +238,10 @@ hipError_t launch_spmv(const Geometry &g, const DeviceArrays &d, int value_type,
 hipError_t launch_spmm(const Geometry &g, const DeviceArrays &d, int value_type, const void *X, int ldx, int k, void *Y, int ldy,
                        void *work, int zero_empty, int xcd_remap, hipStream_t s);
 constexpr int spmm_block_width(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+// csr5_sddmm.hip: out[e] = dot(U[row(e), 0..k-1], V[col(e), 0..k-1]) for every stored element, out in CSR order; rows and columns from
+// the plain tile structure (g, d: CSR5 form); U m x k and V n x k row-major with leading dimensions ldu / ldv; no workspace
+hipError_t launch_sddmm(const Geometry &g, const DeviceArrays &d, int value_type, const void *U, int ldu, const void *V, int ldv, int k,
+                        void *out, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

@@ -70,6 +70,7 @@ class anonymouslibHandle:
     def inputCSR(self, nnz: int, csr_row_pointer, csr_column_index, csr_value) -> int:
         self._keep.update(row_ptr=csr_row_pointer, col=csr_column_index, val=csr_value)
         self._nnz = int(nnz)
+        self._autograd_key = None
         return self._lib.csr5hip_input_csr(self._h, int(nnz), _ptr(csr_row_pointer),
                                            _ptr(csr_column_index), _ptr(csr_value))
 
@@ -164,6 +165,54 @@ class anonymouslibHandle:
         """csr5hip_spmm_t on raw device pointers (or tensors): X with leading dimension ldx, Y with ldy"""
         return self._lib.csr5hip_spmm_t(self._h, _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy))
 
+    # -- sampled dense-dense product on the pattern (csr5hip.h csr5hip_sddmm) ----------------------
+    def sddmm(self, U, V, out) -> int:
+        """out[e] = dot(U[row(e), :], V[col(e), :]) for every stored element e, in CSR order -- the order ``updateValues`` takes.
+        U (m, k) and V (n, k) as ``spmm``'s operands (stride(1) == 1, leading dimension stride(0)); ``out`` a contiguous 1-D GPU
+        tensor of nnz values of the handle's dtype that shares storage with neither U nor V.  The matrix values play no part.
+        With U = dY and V = X this is the gradient of ``spmm`` with respect to the stored values.  Anything else raises
+        ValueError before the library is called."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        for name, t, rows in (("U", U, self._m), ("V", V, self._n)):  # (the checks of _spmm_args; the device comes last)
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"sddmm: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"sddmm: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 2 or t.shape[0] != rows:
+                raise ValueError(f"sddmm: {name} must have shape ({rows}, k), not {tuple(t.shape)}")
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError(f"sddmm: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                raise ValueError(f"sddmm: {name} rows overlap (stride(0) {t.stride(0)} < k = {t.shape[1]})")
+        if U.shape[1] != V.shape[1]:
+            raise ValueError(f"sddmm: U has {U.shape[1]} columns, V {V.shape[1]}")
+        k = int(U.shape[1])
+        ldu = max(int(U.stride(0)), k) if U.shape[0] > 1 else k
+        ldv = max(int(V.stride(0)), k) if V.shape[0] > 1 else k
+        if not hasattr(out, "data_ptr") or not hasattr(out, "is_contiguous"):
+            raise ValueError("sddmm: out must be a torch tensor")
+        if self._nnz is None:
+            raise ValueError("sddmm: call inputCSR first")
+        if str(out.dtype) != dt:
+            raise ValueError(f"sddmm: out has dtype {out.dtype}, the handle holds {dt}")
+        if out.dim() != 1 or out.shape[0] != self._nnz:
+            raise ValueError(f"sddmm: out must have shape ({self._nnz},), not {tuple(out.shape)}")
+        if not out.is_contiguous():
+            raise ValueError(f"sddmm: out must be contiguous, not stride {out.stride()}")
+        for name, t in (("U", U), ("V", V)):
+            if out.numel() and t.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                raise ValueError(f"sddmm: out shares storage with {name} (aliased)")
+        for name, t in (("U", U), ("V", V), ("out", out)):
+            if t.device.type != "cuda":
+                raise ValueError(f"sddmm: {name} must live on the GPU, not {t.device}")
+        if not (U.device == V.device == out.device):
+            raise ValueError(f"sddmm: U on {U.device}, V on {V.device}, out on {out.device}")
+        return self.sddmm_ptr(U, ldu, V, ldv, k, out)
+
+    def sddmm_ptr(self, U, ldu: int, V, ldv: int, k: int, out) -> int:
+        """csr5hip_sddmm on raw device pointers (or tensors): U with leading dimension ldu, V with ldv, out nnz values"""
+        return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
+
     def updateValues(self, val) -> int:
         """New numerical values under the same pattern, without a new conversion (csr5hip.h csr5hip_update_values): ``val`` is a
         contiguous 1-D GPU tensor of the handle's dtype with nnz elements in CSR order -- the order ``inputCSR``'s value tensor
@@ -189,6 +238,7 @@ class anonymouslibHandle:
 
     def updateValues_ptr(self, val) -> int:
         """csr5hip_update_values on a raw device pointer (or tensor)"""
+        self._autograd_key = None  # (autograd.spmm tracks which values the handle holds: these are not the ones it gave)
         return self._lib.csr5hip_update_values(self._h, _ptr(val))
 
     # -- additions (documented in include/csr5hip.h) ---------------------------------------------

@@ -149,6 +149,12 @@ public:
     {
         return _h ? csr5hip_spmm_t(_h, (const void *)X, ldx, k, (void *)Y, ldy) : _err;
     }
+    // extension: out[e] = dot(U[row(e), 0..k-1], V[col(e), 0..k-1]) for every stored element, nnz values in CSR order (the order
+    // updateValues takes); U m x k (ldu), V n x k (ldv), row-major; device pointers; the matrix values play no part (csr5hip_sddmm)
+    int sddmm(const ANONYMOUSLIB_VT *U, int ldu, const ANONYMOUSLIB_VT *V, int ldv, int k, ANONYMOUSLIB_VT *out)
+    {
+        return _h ? csr5hip_sddmm(_h, (const void *)U, ldu, (const void *)V, ldv, k, (void *)out) : _err;
+    }
     int autotuneSigma(ANONYMOUSLIB_VT *y, int *sigma = 0, double *us = 0)
     {
         return _h ? csr5hip_autotune_sigma(_h, (void *)y, sigma, us) : _err;

@@ -283,6 +283,28 @@ int csr5hip_spmv_t(csr5hip_handle h, const void *d_x, void *d_y);
  * column c bit-identical to a two-pass spmv of the transposed matrix with x = X[:, c]); errors as csr5hip_spmm and
  * csr5hip_spmv_t. */
 int csr5hip_spmm_t(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y, int ldy);
+/* Extension (not in the reference): sampled dense-dense product on the matrix' own pattern,
+ *     out[e] = sum_{c < k} U[row(e), c] * V[col(e), c]      for every stored element e of A.
+ * U: m rows x k, row-major, leading dimension ldu >= k; V: n rows x k, row-major, ldv >= k; d_out_csr: nnz values of the handle's
+ * value type in CSR ORDER -- the order inputCSR's value array had and csr5hip_update_values takes (repeated (row, column) pairs
+ * each get their own, equal, output).  Device pointers, element-aligned.  With U = dY and V = X this is the gradient of
+ * Y = A X with respect to A's stored values; csr5hip_spmm_t gives the one for X.
+ * The matrix VALUES play no part: the pattern samples, the values do not scale.  The handle's x, its values, every option,
+ * csr5hip_info and device_bytes are neither read nor changed; nothing is allocated: the call only enqueues work on the handle's
+ * stream, from the first call on (capturable in a caller's graph on that stream).  Rows and columns come from the handle's own
+ * tile structure (tile_ptr, the bit flags, y_offset, the empty-row offsets, the tile-ordered column_index), whatever path spmv()
+ * runs on the handle.
+ * DETERMINISM: out[e] is ONE chain of k fused multiply-adds in ascending column order onto +0,
+ *     fma(U[r][k-1], V[j][k-1], ... fma(U[r][1], V[j][1], fma(U[r][0], V[j][0], +0)) ...),
+ * so it depends only on the k values of U's row, the k values of V's row, k and the value type: not on sigma, any option, the
+ * element's position or the kind of tile that holds it, ldu / ldv, pointer alignment or the run.  A dot product is computed
+ * from its own two rows only (Inf and NaN stay with the elements whose rows hold them); subnormals are not flushed.
+ * k = 0 writes +0 into all nnz outputs; nnz = 0 is a successful no-op.  d_out_csr must not overlap U, V or any array of the
+ * handle (the CSR arrays given to inputCSR included); U and V may be the same array.
+ * Returns, in this order: CSR5HIP_INVALID_ARGUMENT for a null handle, k < 0, ldu < k, ldv < k, a null U or V with k > 0 and
+ * nnz > 0, or a null d_out_csr with nnz > 0; CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format; CSR5HIP_UNKOWN_FORMAT before inputCSR.
+ * Single handles only: csr5hip_multi has no sddmm (a shard holds a row block: call it on the shard handles with U's row block). */
+int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, int ldv, int k, void *d_out_csr);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
