@@ -1,4 +1,6 @@
-"""A converted handle as a differentiable sparse operator: ``Y = spmm(A, val, X)`` with gradients for ``val`` and ``X``.
+"""A converted handle as a differentiable sparse operator: ``Y = spmm(A, val, X)`` with gradients for ``val`` and ``X``, the
+two other links of attention on the pattern -- ``sddmm(A, U, V)`` and ``row_softmax(A, scores)`` -- and their composition
+``attention(A, Q, K, V)``.
 
 ``A`` is an ``anonymouslibHandle`` in CSR5 format, ``val`` its nnz values in CSR order (the order ``inputCSR``'s value tensor
 had) and ``X`` an (n, k) tensor; fp64 and fp32.  The three legs are the library's own kernels:
@@ -18,6 +20,13 @@ gradient: ``sddmm`` does not read the values).
 Aliasing (inherited from ``updateValues``): ``val`` must not share storage with the tensor given to ``inputCSR`` -- the handle
 keeps that one in its own order; ``updateValues`` raises ValueError.
 
+``row_softmax(A, scores)`` is ``A.rowSoftmax`` forward (the output p is saved) and ``A.rowSoftmaxGrad(p, g)`` backward; it reads
+the handle's row_ptr only.  ``sddmm(A, U, V)`` is ``A.sddmm`` forward; backward hands the handle the incoming gradient G as its
+values and takes ``grad_U = A.spmm(V)`` and ``grad_V = A.spmmT(U)``, each into ``torch.zeros`` and only where needed (the
+transposed companion is built only when V needs a gradient).  After any of these calls the handle HOLDS WHATEVER VALUES THE LAST
+CALL GAVE IT -- ``spmm``'s val, or a gradient G from ``sddmm``'s backward; ``spmm``'s backward gives the forward's values again
+where it needs them (above), so interleaved forwards and backwards on one handle stay correct.
+
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
 """
@@ -27,7 +36,7 @@ import torch
 
 from . import _capi
 
-__all__ = ["spmm"]
+__all__ = ["spmm", "sddmm", "row_softmax", "attention"]
 
 
 def _check(rc: int, what: str) -> None:
@@ -98,3 +107,79 @@ def spmm(A, val, X):
     """Y = A X (m, k) with the values ``val`` (nnz, CSR order) on the pattern of the converted handle ``A``; differentiable in
     ``val`` and ``X`` (see the module docstring)."""
     return _Spmm.apply(A, val, X)
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, U, V):
+        Uc, Vc = _rows_unit_stride(U.detach()), _rows_unit_stride(V.detach())
+        _on_current_stream(A, Uc.device)
+        out = torch.empty(A._nnz, dtype=Uc.dtype, device=Uc.device)
+        _check(A.sddmm(Uc, Vc, out), "sddmm")
+        ctx.A = A
+        ctx.save_for_backward(Uc, Vc)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        A = ctx.A
+        U, V = ctx.saved_tensors
+        need_U, need_V = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_U = grad_V = None
+        if not (need_U or need_V):
+            return None, None, None
+        G = G.detach().contiguous()
+        _on_current_stream(A, G.device)
+        _give_values(A, G, _key(G))  # (the handle now holds G: see the module docstring)
+        if need_U:  # dU[i, :] = sum_j G[i, j] V[j, :]
+            grad_U = torch.zeros((A._m, V.shape[1]), dtype=G.dtype, device=G.device)
+            _check(A.spmm(V, grad_U), "spmm")
+        if need_V:  # dV[j, :] = sum_i G[i, j] U[i, :]
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            grad_V = torch.zeros((A._n, U.shape[1]), dtype=G.dtype, device=G.device)
+            _check(A.spmmT(U, grad_V), "spmmT")
+        return None, grad_U, grad_V
+
+
+class _RowSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, scores):
+        s = scores.detach().contiguous()
+        _on_current_stream(A, s.device)
+        p = torch.empty_like(s)
+        _check(A.rowSoftmax(s, p), "rowSoftmax")
+        ctx.A = A
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        A = ctx.A
+        (p,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        g = g.detach().contiguous()
+        _on_current_stream(A, g.device)
+        out = torch.empty_like(p)
+        _check(A.rowSoftmaxGrad(p, g, out), "rowSoftmaxGrad")
+        return None, out
+
+
+def sddmm(A, U, V):
+    """out[e] = dot(U[row(e), :], V[col(e), :]) for every stored element of the converted handle ``A`` (nnz values, CSR order);
+    differentiable in ``U`` (m, k) and ``V`` (n, k) (see the module docstring)."""
+    return _Sddmm.apply(A, U, V)
+
+
+def row_softmax(A, scores):
+    """softmax of ``scores`` (nnz, CSR order) over the stored entries of every row of the handle ``A``; differentiable in
+    ``scores``."""
+    return _RowSoftmax.apply(A, scores)
+
+
+def attention(A, Q, K, V):
+    """sparse attention on the pattern of the converted handle ``A``: row i attends to the columns j it stores, with weights
+    softmax_j(Q[i, :] . K[j, :]).  Q (m, k), K (n, k), V (n, d); differentiable in all three.  Any scaling (1 / sqrt(k)) is
+    applied by the caller to Q."""
+    return spmm(A, row_softmax(A, sddmm(A, Q, K)), V)

@@ -1676,6 +1676,40 @@ int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, i
     return CSR5HIP_SUCCESS;
 }
 
+// Softmax over the stored entries of every row, and its gradient (csr5_softmax.hip): nnz values in CSR order in, nnz out.  They read
+// row_ptr and nothing else of the handle, so CSR and CSR5 format are served alike; nothing is allocated or changed: enqueue-only.
+int csr5hip_row_softmax(csr5hip_handle h, const void *d_scores_csr, void *d_out_csr)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool loaded = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5;
+    const int nnz = loaded ? h->g.nnz : 0;
+    if (nnz > 0 && (!d_scores_csr || !d_out_csr))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (!loaded)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (nnz == 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_row_softmax(h->g.m, h->d.row_ptr, h->value_type, d_scores_csr, d_out_csr, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
+int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *d_g_csr, void *d_out_csr)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool loaded = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5;
+    const int nnz = loaded ? h->g.nnz : 0;
+    if (nnz > 0 && (!d_p_csr || !d_g_csr || !d_out_csr))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (!loaded)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (nnz == 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_row_softmax_grad(h->g.m, h->d.row_ptr, h->value_type, d_p_csr, d_g_csr, d_out_csr, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

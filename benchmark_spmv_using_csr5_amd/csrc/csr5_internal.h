@@ -242,6 +242,11 @@ constexpr int spmm_block_width(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 
 // the plain tile structure (g, d: CSR5 form); U m x k and V n x k row-major with leading dimensions ldu / ldv; no workspace
 hipError_t launch_sddmm(const Geometry &g, const DeviceArrays &d, int value_type, const void *U, int ldu, const void *V, int ldv, int k,
                         void *out, hipStream_t s);
+// csr5_softmax.hip: softmax over the stored entries of every row and its gradient, nnz values in CSR order; row_ptr is all they read
+// of the matrix (CSR and CSR5 format alike); no workspace
+hipError_t launch_row_softmax(int m, const int32_t *row_ptr, int value_type, const void *scores, void *out, hipStream_t s);
+hipError_t launch_row_softmax_grad(int m, const int32_t *row_ptr, int value_type, const void *p, const void *g, void *out,
+                                   hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

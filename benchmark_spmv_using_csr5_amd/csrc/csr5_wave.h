@@ -66,6 +66,22 @@ __device__ __forceinline__ VT wave_sum(VT v)
     v += dpp_move<DPP_ROW_BCAST31>(v);              // rows 2,3 += lane 31 -> lane 63 = wave sum
     return bcast_lane(v, OMEGA - 1);
 }
+// the larger of two values, a NaN operand skipped (IEEE maxNum)
+__device__ __forceinline__ float max_vt(float a, float b) { return __builtin_fmaxf(a, b); }
+__device__ __forceinline__ double max_vt(double a, double b) { return __builtin_fmax(a, b); }
+// maximum over the 64 lanes, result in every lane: wave_sum's steps.  The zeros that bound_ctrl shifts in from outside a row
+// only reach lanes that lane 63's chain (lanes 15 / 31 / 47 / 63 of full windows) never reads.
+template <typename VT>
+__device__ __forceinline__ VT wave_max(VT v)
+{
+    v = max_vt(v, dpp_move<DPP_ROW_SHR1>(v));
+    v = max_vt(v, dpp_move<DPP_ROW_SHR2>(v));
+    v = max_vt(v, dpp_move<DPP_ROW_SHR4>(v));
+    v = max_vt(v, dpp_move<DPP_ROW_SHR8>(v));
+    v = max_vt(v, dpp_move<DPP_ROW_BCAST15>(v));
+    v = max_vt(v, dpp_move<DPP_ROW_BCAST31>(v));
+    return bcast_lane(v, OMEGA - 1);
+}
 // bitwise OR over the 64 lanes, result wave-uniform (same DPP steps as wave_sum)
 __device__ __forceinline__ uint32_t wave_or(uint32_t w)
 {

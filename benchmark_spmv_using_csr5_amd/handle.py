@@ -213,6 +213,57 @@ class anonymouslibHandle:
         """csr5hip_sddmm on raw device pointers (or tensors): U with leading dimension ldu, V with ldv, out nnz values"""
         return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
 
+    # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
+    def _csr_value_args(self, who: str, named) -> None:
+        """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless
+        each is a contiguous 1-D GPU tensor of nnz values of the handle's dtype, the output shares storage with no input, and
+        all live on one device"""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        for name, t in named:
+            if not hasattr(t, "data_ptr") or not hasattr(t, "is_contiguous"):
+                raise ValueError(f"{who}: {name} must be a torch tensor")
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        for name, t in named:
+            if str(t.dtype) != dt:
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 1 or t.shape[0] != self._nnz:
+                raise ValueError(f"{who}: {name} must have shape ({self._nnz},), not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous, not stride {t.stride()}")
+        out_name, out = named[-1]
+        for name, t in named[:-1]:
+            if out.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                raise ValueError(f"{who}: {out_name} shares storage with {name} (aliased)")
+        for name, t in named:
+            if t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        if any(t.device != out.device for _, t in named):
+            raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t in named))
+
+    def rowSoftmax(self, scores, out) -> int:
+        """out[e] = exp(scores[e] - max of the row) / sum over the row, for every stored element, in CSR order -- the order
+        ``sddmm`` writes and ``updateValues`` takes.  ``scores`` and ``out`` are contiguous 1-D GPU tensors of nnz values of the
+        handle's dtype that share no storage.  Legal in CSR and CSR5 format alike; allocates nothing; non-finite scores behave
+        as in ``torch.softmax``.  Anything else raises ValueError before the library is called."""
+        self._csr_value_args("rowSoftmax", (("scores", scores), ("out", out)))
+        return self.rowSoftmax_ptr(scores, out)
+
+    def rowSoftmax_ptr(self, scores, out) -> int:
+        """csr5hip_row_softmax on raw device pointers (or tensors): nnz values each"""
+        return self._lib.csr5hip_row_softmax(self._h, _ptr(scores), _ptr(out))
+
+    def rowSoftmaxGrad(self, p, g, out) -> int:
+        """out[e] = p[e] * (g[e] - sum over the row of p * g): the gradient of ``rowSoftmax`` for its scores, from its output p and
+        the gradient g arriving for p.  Arguments as ``rowSoftmax``; p and g may be the same tensor, ``out`` shares storage with
+        neither."""
+        self._csr_value_args("rowSoftmaxGrad", (("p", p), ("g", g), ("out", out)))
+        return self.rowSoftmaxGrad_ptr(p, g, out)
+
+    def rowSoftmaxGrad_ptr(self, p, g, out) -> int:
+        """csr5hip_row_softmax_grad on raw device pointers (or tensors): nnz values each"""
+        return self._lib.csr5hip_row_softmax_grad(self._h, _ptr(p), _ptr(g), _ptr(out))
+
     def updateValues(self, val) -> int:
         """New numerical values under the same pattern, without a new conversion (csr5hip.h csr5hip_update_values): ``val`` is a
         contiguous 1-D GPU tensor of the handle's dtype with nnz elements in CSR order -- the order ``inputCSR``'s value tensor

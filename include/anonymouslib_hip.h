@@ -155,6 +155,16 @@ public:
     {
         return _h ? csr5hip_sddmm(_h, (const void *)U, ldu, (const void *)V, ldv, k, (void *)out) : _err;
     }
+    // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
+    // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
+    int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)
+    {
+        return _h ? csr5hip_row_softmax(_h, (const void *)scores, (void *)out) : _err;
+    }
+    int rowSoftmaxGrad(const ANONYMOUSLIB_VT *p, const ANONYMOUSLIB_VT *g, ANONYMOUSLIB_VT *out)
+    {
+        return _h ? csr5hip_row_softmax_grad(_h, (const void *)p, (const void *)g, (void *)out) : _err;
+    }
     int autotuneSigma(ANONYMOUSLIB_VT *y, int *sigma = 0, double *us = 0)
     {
         return _h ? csr5hip_autotune_sigma(_h, (void *)y, sigma, us) : _err;

@@ -305,6 +305,37 @@ int csr5hip_spmm_t(csr5hip_handle h, const void *d_X, int ldx, int k, void *d_Y,
  * nnz > 0, or a null d_out_csr with nnz > 0; CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format; CSR5HIP_UNKOWN_FORMAT before inputCSR.
  * Single handles only: csr5hip_multi has no sddmm (a shard holds a row block: call it on the shard handles with U's row block). */
 int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, int ldv, int k, void *d_out_csr);
+/* Extension (not in the reference): softmax over the stored entries of every row ("edge softmax") and its gradient, on arrays of
+ * nnz values of the handle's value type in CSR ORDER (the order inputCSR's value array had, csr5hip_sddmm writes and
+ * csr5hip_update_values takes):
+ *     csr5hip_row_softmax        out[e] = exp(s[e] - M_r) / Z_r,   M_r = max of the row's scores, Z_r = sum_row exp(s[j] - M_r)
+ *     csr5hip_row_softmax_grad   out[e] = p[e] * (g[e] - D_r),     D_r = sum_row p[j] * g[j]   (p: the forward's output,
+ *                                                                   g: the gradient arriving for it)
+ * Device pointers, element-aligned.  d_out_csr must not overlap an input or any array of the handle; d_p_csr and d_g_csr may be
+ * the same array.  Both read the handle's row_ptr and NOTHING else (no columns, values, x, tile structure or kernel table), so
+ * they are legal in CSR and in CSR5 format alike.  Nothing is allocated and nothing in the handle changes (csr5hip_info,
+ * device_bytes, the values, x and the options stay as they are); the call only enqueues work on the handle's stream, from the
+ * first call on (capturable in a caller's graph on that stream; no pre-pass, nothing read back).
+ * DEFINITION: M is the exact maximum of the row; a term is one subtraction and one exponential (the device library's full
+ * precision exp / expf, subnormal results kept); the quotient is ONE RECIPROCAL PER ROW, r = 1 / Z (correctly rounded), and ONE
+ * MULTIPLICATION PER ENTRY.  The gradient rounds each p[j] * g[j], then g[e] - D, then the product with p[e]; no fused
+ * multiply-add, no rescaled running maximum.  D is computed from the row's own entries only.
+ * Empty rows write nothing; a finite row of one entry gives exactly 1.  NON-FINITE values follow torch.softmax: a -Inf score gets
+ * exactly +0; a row that holds a NaN, holds a +Inf or consists only of -Inf gives NaN in every entry of that row and in no other.
+ * TREE of Z and of D, a function of the row's length L alone.  L <= 512: slot(j) = j mod 64; every slot adds its terms j = slot,
+ * slot + 64, ... in ascending order onto +0; the 64 slot sums (+0 where a slot has no term) are added by the balanced binary tree
+ * over adjacent slots (pairs (0,1) (2,3) ..., quads, ..., the two halves).  L > 512: slot(j) = j mod 256, slots 64 w .. 64 w + 63
+ * by that balanced tree for w = 0 .. 3, then (w0 + w1) + (w2 + w3).
+ * DETERMINISM: the bits of a row's outputs depend only on that row's inputs (values and order) and on the value type: not on
+ * sigma, any option or the format, pointer alignment, m, nnz, the position of the row in the matrix, what neighbouring rows
+ * hold, or the run.
+ * A row is worked on by at most one workgroup (rows beyond 512 entries by its four wavefronts together), so one very long row
+ * runs at one workgroup's bandwidth.
+ * Returns, decided on the host in this order: CSR5HIP_INVALID_ARGUMENT for a null handle or any null pointer while nnz > 0;
+ * CSR5HIP_UNKOWN_FORMAT before inputCSR.  nnz = 0 is a successful no-op that touches no device.
+ * Single handles only: csr5hip_multi has none (a shard holds whole rows: call them on the shard handles). */
+int csr5hip_row_softmax(csr5hip_handle h, const void *d_scores_csr, void *d_out_csr);
+int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *d_g_csr, void *d_out_csr);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
