@@ -27,6 +27,11 @@ transposed companion is built only when V needs a gradient).  After any of these
 CALL GAVE IT -- ``spmm``'s val, or a gradient G from ``sddmm``'s backward; ``spmm``'s backward gives the forward's values again
 where it needs them (above), so interleaved forwards and backwards on one handle stay correct.
 
+``fused_attention(A, Q, K, V)`` is the same function as ``attention`` with a one-launch forward: ``A.attention`` into
+``torch.empty``, nothing of length nnz allocated, only Q, K and V saved, the handle's values and the record of them untouched
+(the forward of inference, under ``torch.no_grad()``, where the values in the handle belong to somebody else).  Its backward
+recomputes through ``attention`` and therefore DOES leave the handle as that function's backward does (below).
+
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
 """
@@ -36,7 +41,7 @@ import torch
 
 from . import _capi
 
-__all__ = ["spmm", "sddmm", "row_softmax", "attention"]
+__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention"]
 
 
 def _check(rc: int, what: str) -> None:
@@ -183,3 +188,42 @@ def attention(A, Q, K, V):
     softmax_j(Q[i, :] . K[j, :]).  Q (m, k), K (n, k), V (n, d); differentiable in all three.  Any scaling (1 / sqrt(k)) is
     applied by the caller to Q."""
     return spmm(A, row_softmax(A, sddmm(A, Q, K)), V)
+
+
+class _FusedAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V):
+        Qc, Kc, Vc = (_rows_unit_stride(t.detach()) for t in (Q, K, V))
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m, Vc.shape[1]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row)
+        _check(A.attention(Qc, Kc, Vc, O), "attention")
+        ctx.A = A
+        ctx.save_for_backward(Qc, Kc, Vc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        need = ctx.needs_input_grad[1:4]
+        if not any(need):
+            return None, None, None, None
+        with torch.enable_grad():
+            ops = [t.detach().requires_grad_(True) if n else t for t, n in zip(ctx.saved_tensors, need)]
+            out = attention(ctx.A, *ops)
+            grads = iter(torch.autograd.grad(out, [t for t, n in zip(ops, need) if n], dO))
+        return (None,) + tuple(next(grads) if n else None for n in need)
+
+
+def fused_attention(A, Q, K, V):
+    """``attention(A, Q, K, V)`` -- the same function, the same gradients -- with the forward in ONE launch (``A.attention``): no
+    scores, no weights, nothing of length nnz is allocated or written, and only Q, K and V are kept for backward.  The forward
+    neither reads nor changes the handle's values and does not touch the record of them, so under ``torch.no_grad()`` the
+    handle is exactly what it was.  The output agrees with ``attention``'s to rounding, not bit for bit (the normalisation
+    comes after the product, and the product is summed row-wise).
+
+    Backward recomputes the weights through the existing pieces: ``attention`` on detached copies of exactly those operands
+    that need a gradient, then ``torch.autograd.grad`` with the incoming gradient, so the three gradients are bit for bit
+    those of ``attention`` for the same inputs.  The rules of that function therefore apply AFTER A BACKWARD: the handle holds
+    whatever values the last call gave it (the recomputed weights, or a gradient from ``sddmm``'s backward), and the transposed
+    companion is built (once per conversion: it allocates and synchronises) only when K or V needs a gradient.  Nothing runs
+    in backward when no input needs a gradient."""
+    return _FusedAttention.apply(A, Q, K, V)

@@ -1710,6 +1710,28 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
     return CSR5HIP_SUCCESS;
 }
 
+// O = softmax over every row's stored entries of (Q K^T) times V, in one launch (csr5_attention.hip).  Reads row_ptr, tile_ptr and the
+// tile-ordered column_index of the parent, whatever path spmv() takes; allocates nothing, changes nothing: enqueue-only.
+int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
+                      void *d_O, int ldo)
+{
+    if (!h || k < 0 || d < 0 || ldq < k || ldk < k || ldv < d || ldo < d)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (d > 0 && h->g.m > 0 && !d_O)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (d == 0 || h->g.m <= 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_attention(h->g, h->d, h->value_type, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

@@ -247,6 +247,10 @@ hipError_t launch_sddmm(const Geometry &g, const DeviceArrays &d, int value_type
 hipError_t launch_row_softmax(int m, const int32_t *row_ptr, int value_type, const void *scores, void *out, hipStream_t s);
 hipError_t launch_row_softmax_grad(int m, const int32_t *row_ptr, int value_type, const void *p, const void *g, void *out,
                                    hipStream_t s);
+// csr5_attention.hip: O = softmax_row(Q K^T on the pattern) V in one pass, nothing of length nnz written; reads row_ptr, tile_ptr and
+// the tile-ordered column_index (g, d: CSR5 form) and writes EVERY row of O in columns 0 .. dcols-1; no workspace
+hipError_t launch_attention(const Geometry &g, const DeviceArrays &d, int value_type, const void *Q, int ldq, const void *K, int ldk,
+                            int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

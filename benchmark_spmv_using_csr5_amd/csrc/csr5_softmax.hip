@@ -57,60 +57,6 @@ constexpr int SM_REGS = 8;                    // entries of a row a lane keeps i
 constexpr int SM_WAVE_ROW = OMEGA * SM_REGS;  // rows up to 512 entries: one wavefront, in registers
 constexpr int SM_BLOCK_REG_ROW = SM_BLOCK * SM_REGS; // rows up to 2 048 entries: the workgroup, in registers; beyond: sweeps
 
-constexpr int DPP_QUAD_XOR1 = 0xB1;     // quad_perm [1, 0, 3, 2]
-constexpr int DPP_QUAD_XOR2 = 0x4E;     // quad_perm [2, 3, 0, 1]
-constexpr int DPP_ROW_HALF_MIRROR = 0x141; // lane i of every 8 reads lane 7 - i
-constexpr int DPP_ROW_MIRROR = 0x140;      // lane i of every 16 reads lane 15 - i
-
-__device__ __forceinline__ float exp_vt(float v) { return expf(v); }
-__device__ __forceinline__ double exp_vt(double v) { return exp(v); }
-template <typename VT>
-__device__ __forceinline__ VT neg_inf()
-{
-    return -(VT)__builtin_inff();
-}
-
-// sum / maximum over aligned groups of G = 4 or 16 lanes, result in every lane of the group.  Butterfly steps on DPP: after the
-// quad steps the lanes of a quad agree, so the mirror of 8 hands over the neighbouring quad's value, the mirror of 16 the other
-// half's.  By commutativity this is the balanced tree over adjacent lanes -- the leading sub-tree of wave_sum.
-template <int G, typename VT>
-__device__ __forceinline__ VT group_sum(VT v)
-{
-    v += dpp_move<DPP_QUAD_XOR1>(v);
-    v += dpp_move<DPP_QUAD_XOR2>(v);
-    if constexpr (G == 16) {
-        v += dpp_move<DPP_ROW_HALF_MIRROR>(v);
-        v += dpp_move<DPP_ROW_MIRROR>(v);
-    }
-    return v;
-}
-template <int G, typename VT>
-__device__ __forceinline__ VT group_max(VT v)
-{
-    v = max_vt(v, dpp_move<DPP_QUAD_XOR1>(v));
-    v = max_vt(v, dpp_move<DPP_QUAD_XOR2>(v));
-    if constexpr (G == 16) {
-        v = max_vt(v, dpp_move<DPP_ROW_HALF_MIRROR>(v));
-        v = max_vt(v, dpp_move<DPP_ROW_MIRROR>(v));
-    }
-    return v;
-}
-
-// (w0 + w1) + (w2 + w3) / the maximum of the four wavefront results, in every lane of the workgroup; red: SM_WAVES values in LDS
-template <typename VT, bool MAX>
-__device__ __forceinline__ VT block_combine(VT mine, VT *red)
-{
-    if ((threadIdx.x & (OMEGA - 1)) == 0)
-        red[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    const VT a = red[0], b = red[1], c = red[2], d = red[3];
-    __syncthreads(); // (red is free for the next reduction)
-    if constexpr (MAX)
-        return max_vt(max_vt(a, b), max_vt(c, d));
-    else
-        return (a + b) + (c + d);
-}
-
 // ---- rows of at most G entries (and more than LO): G lanes per row, 64 / G rows of the wavefront per pass -----------------
 template <typename VT, bool GRAD, int G, int LO>
 __device__ __forceinline__ void softmax_short(const int a, const int len, const VT *__restrict__ in, const VT *__restrict__ gin,

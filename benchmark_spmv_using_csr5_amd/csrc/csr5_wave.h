@@ -1,7 +1,10 @@
-// csr5_wave.h -- wave64 cross-lane helpers shared by the SpMV kernels (csr5_spmv.hip, csr5_hot.hip); gfx950 only.
+// csr5_wave.h -- wave64 cross-lane helpers shared by the SpMV kernels (csr5_spmv.hip, csr5_hot.hip) and the row-wise kernels
+// (csr5_softmax.hip, csr5_attention.hip); gfx950 only.
 #pragma once
 
 #include "csr5_internal.h"
+
+#include <math.h>
 
 namespace csr5 {
 
@@ -82,6 +85,61 @@ __device__ __forceinline__ VT wave_max(VT v)
     v = max_vt(v, dpp_move<DPP_ROW_BCAST31>(v));
     return bcast_lane(v, OMEGA - 1);
 }
+// ---- pieces of the row-wise kernels (csr5_softmax.hip, csr5_attention.hip) ----------------------------------------------------
+constexpr int DPP_QUAD_XOR1 = 0xB1;     // quad_perm [1, 0, 3, 2]
+constexpr int DPP_QUAD_XOR2 = 0x4E;     // quad_perm [2, 3, 0, 1]
+constexpr int DPP_ROW_HALF_MIRROR = 0x141; // lane i of every 8 reads lane 7 - i
+constexpr int DPP_ROW_MIRROR = 0x140;      // lane i of every 16 reads lane 15 - i
+
+__device__ __forceinline__ float exp_vt(float v) { return expf(v); }
+__device__ __forceinline__ double exp_vt(double v) { return exp(v); }
+template <typename VT>
+__device__ __forceinline__ VT neg_inf()
+{
+    return -(VT)__builtin_inff();
+}
+
+// sum / maximum over aligned groups of G = 4 or 16 lanes, result in every lane of the group.  Butterfly steps on DPP: after the
+// quad steps the lanes of a quad agree, so the mirror of 8 hands over the neighbouring quad's value, the mirror of 16 the other
+// half's.  By commutativity this is the balanced tree over adjacent lanes -- the leading sub-tree of wave_sum.
+template <int G, typename VT>
+__device__ __forceinline__ VT group_sum(VT v)
+{
+    v += dpp_move<DPP_QUAD_XOR1>(v);
+    v += dpp_move<DPP_QUAD_XOR2>(v);
+    if constexpr (G == 16) {
+        v += dpp_move<DPP_ROW_HALF_MIRROR>(v);
+        v += dpp_move<DPP_ROW_MIRROR>(v);
+    }
+    return v;
+}
+template <int G, typename VT>
+__device__ __forceinline__ VT group_max(VT v)
+{
+    v = max_vt(v, dpp_move<DPP_QUAD_XOR1>(v));
+    v = max_vt(v, dpp_move<DPP_QUAD_XOR2>(v));
+    if constexpr (G == 16) {
+        v = max_vt(v, dpp_move<DPP_ROW_HALF_MIRROR>(v));
+        v = max_vt(v, dpp_move<DPP_ROW_MIRROR>(v));
+    }
+    return v;
+}
+
+// (w0 + w1) + (w2 + w3) / the maximum of the four wavefront results, in every lane of a workgroup of 256 lanes; red: 4 values in LDS
+template <typename VT, bool MAX>
+__device__ __forceinline__ VT block_combine(VT mine, VT *red)
+{
+    if ((threadIdx.x & (OMEGA - 1)) == 0)
+        red[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    const VT a = red[0], b = red[1], c = red[2], d = red[3];
+    __syncthreads(); // (red is free for the next reduction)
+    if constexpr (MAX)
+        return max_vt(max_vt(a, b), max_vt(c, d));
+    else
+        return (a + b) + (c + d);
+}
+
 // bitwise OR over the 64 lanes, result wave-uniform (same DPP steps as wave_sum)
 __device__ __forceinline__ uint32_t wave_or(uint32_t w)
 {

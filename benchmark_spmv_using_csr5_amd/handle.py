@@ -213,6 +213,50 @@ class anonymouslibHandle:
         """csr5hip_sddmm on raw device pointers (or tensors): U with leading dimension ldu, V with ldv, out nnz values"""
         return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
 
+    # -- attention on the pattern in one pass (csr5hip.h csr5hip_attention) -------------------------
+    def attention(self, Q, K, V, O) -> int:
+        """O = softmax over every row's stored entries of (Q K^T) times V in ONE launch: row i attends to the columns it stores.
+        Q (m, k), K (n, k), V (n, d) and O (m, d) as ``sddmm``'s operands (stride(1) == 1, leading dimension stride(0), so column
+        slices of wider tensors are legal: one call per head needs no copy); O shares storage with none of the inputs, which may
+        share among themselves.  EVERY row of O is written in columns 0 .. d-1 -- rows without entries with +0 -- so O may be
+        ``torch.empty``.  Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything
+        else raises ValueError before the library is called."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        named = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("O", O, self._m, "d"))
+        for name, t, rows, width in named:  # (the checks of sddmm's operands; the device comes last)
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"attention: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"attention: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 2 or t.shape[0] != rows:
+                raise ValueError(f"attention: {name} must have shape ({rows}, {width}), not {tuple(t.shape)}")
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError(f"attention: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                raise ValueError(f"attention: {name} rows overlap (stride(0) {t.stride(0)} < {width} = {t.shape[1]})")
+        if Q.shape[1] != K.shape[1]:
+            raise ValueError(f"attention: Q has {Q.shape[1]} columns, K {K.shape[1]}")
+        if V.shape[1] != O.shape[1]:
+            raise ValueError(f"attention: V has {V.shape[1]} columns, O {O.shape[1]}")
+        if self._nnz is None:
+            raise ValueError("attention: call inputCSR first")
+        k, d = int(Q.shape[1]), int(V.shape[1])
+        ld = [max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1]) for _, t, _, _ in named]
+        for name, t, _, _ in named[:3]:
+            if O.numel() and t.numel() and O.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                raise ValueError(f"attention: O shares storage with {name} (aliased)")
+        for name, t, _, _ in named:
+            if t.device.type != "cuda":
+                raise ValueError(f"attention: {name} must live on the GPU, not {t.device}")
+        if not (Q.device == K.device == V.device == O.device):
+            raise ValueError(f"attention: Q on {Q.device}, K on {K.device}, V on {V.device}, O on {O.device}")
+        return self.attention_ptr(Q, ld[0], K, ld[1], k, V, ld[2], d, O, ld[3])
+
+    def attention_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
+        """csr5hip_attention on raw device pointers (or tensors): Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
+        return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                           _ptr(O), int(ldo))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

@@ -155,6 +155,15 @@ public:
     {
         return _h ? csr5hip_sddmm(_h, (const void *)U, ldu, (const void *)V, ldv, k, (void *)out) : _err;
     }
+    // extension: attention on the pattern in one pass, O = softmax_row(Q K^T on the pattern) V with nothing of length nnz written and
+    // the handle untouched; Q m x k (ldq), K n x k (ldk), V n x d (ldv), O m x d (ldo), row-major device pointers; EVERY row of O is
+    // written in columns 0 .. d-1, rows without entries with +0 (csr5hip_attention)
+    int attention(const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv,
+                  int d, ANONYMOUSLIB_VT *O, int ldo)
+    {
+        return _h ? csr5hip_attention(_h, (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d, (void *)O, ldo)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

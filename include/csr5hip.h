@@ -336,6 +336,48 @@ int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, i
  * Single handles only: csr5hip_multi has none (a shard holds whole rows: call them on the shard handles). */
 int csr5hip_row_softmax(csr5hip_handle h, const void *d_scores_csr, void *d_out_csr);
 int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *d_g_csr, void *d_out_csr);
+/* Extension (not in the reference): attention on the matrix' own pattern in ONE pass -- scores, softmax over the row, product:
+ *     s_e     = sum_{c < k} Q[i, c] * K[j_e, c]          for the stored entries e of row i in CSR order, j_e the column of e
+ *     O[i, c] = (sum_e exp(s_e - M_i) * V[j_e, c]) / Z_i,   M_i = max_e s_e,  Z_i = sum_e exp(s_e - M_i),   c < d
+ * i.e. what csr5hip_sddmm -> csr5hip_row_softmax -> csr5hip_update_values -> csr5hip_spmm compute, without anything of length nnz
+ * written to memory and without touching the handle: its values, x, options, csr5hip_info and device_bytes are neither read nor
+ * changed (the matrix VALUES play no part), nothing is allocated, nothing is read back.  The call only enqueues one kernel on the
+ * handle's stream, from the first call on (capturable in a caller's graph on that stream).
+ * Q: m x k (ldq >= k), K: n x k (ldk >= k), V: n x d (ldv >= d), O: m x d (ldo >= d); all row-major, device pointers,
+ * element-aligned, of the handle's value type.  Column slices of wider tensors are legal operands (one call per head on
+ * Q[:, h k .. (h + 1) k) with ldq = H k needs no copy).  O must not overlap Q, K, V or any array of the handle; Q, K and V may be
+ * the same array.  Repeated (row, column) pairs are separate entries.
+ * EVERY row of O is written in columns 0 .. d-1: a row without entries gets +0 -- unlike csr5hip_spmm, which leaves such rows
+ * alone -- so O may be uninitialised memory.  Columns d .. ldo-1 are never written.
+ * k = 0 makes every score +0: each output is the mean of the row's V rows.  d = 0 or m = 0 is a successful no-op; nnz = 0 with
+ * d > 0 writes the zeros.
+ * DEFINITION: s_e is csr5hip_sddmm's chain of k fused multiply-adds in ascending column order onto +0, the same bits; M is the
+ * exact maximum of the row; a weight w_e = exp(s_e - M) is ONE subtraction and ONE exponential (the device library's full
+ * precision exp / expf, subnormal results kept).  THE NORMALISATION COMES AFTER THE PRODUCT: acc_c = sum_e w_e V[j_e, c] by fused
+ * multiply-adds, ONE reciprocal per row r = 1 / Z (correctly rounded) and ONE multiplication per output, O[i, c] = acc_c * r.  No
+ * running maximum is rescaled.
+ * NON-FINITE values behave as the unfused chain: a -Inf score has weight +0; a row that holds a NaN score, holds a +Inf score or
+ * consists only of -Inf scores is NaN in all d outputs, and no other row is affected.
+ * SUMMATION ORDER, a function of (L, d) alone, L the row's length and j an entry's rank inside its row.
+ *   Z:  csr5hip_row_softmax's tree.  L <= 512: slot(j) = j mod 64, every slot adds its terms in ascending order onto +0, the 64
+ *       slot sums (+0 where a slot has no term) by the balanced binary tree over adjacent slots.  L > 512: slot(j) = j mod 256,
+ *       slots 64 w .. 64 w + 63 by that tree for w = 0 .. 3, then (w0 + w1) + (w2 + w3).
+ *   acc_c, L <= 16: one chain acc = fma(w_j, V[j_j, c], acc) over j = 0 .. L-1 onto +0.
+ *   acc_c, L > 16:  column c lies in block b = c / 64 of width wb = min(64, d - 64 b); C = the smallest power of two >= wb;
+ *       S = 64 / C slots for L <= 512 and 256 / C for L > 512; slot(j) = j mod S; every slot runs one such chain over its j in
+ *       ascending order onto +0; the S slot sums (+0 where a slot has no term) by the balanced binary tree over adjacent slots.
+ * DETERMINISM: the bits of row i of O depend only on Q's row i, the K and V rows of the row's columns in their CSR order, k, d
+ * and the value type: not on sigma, any option, the kind of tile that holds the row's entries, the row's position, its
+ * neighbours, m, n, nnz, the leading dimensions, pointer alignment or the run.
+ * A row is worked on by at most one workgroup (rows up to 16 entries by 16 lanes, up to 512 by one wavefront, longer ones by the
+ * four wavefronts together; beyond 2 048 entries the scores are computed twice), so one very long row runs at one workgroup's
+ * rate.
+ * Returns, decided on the host in this order: CSR5HIP_INVALID_ARGUMENT for a null handle, k < 0, d < 0, ldq < k, ldk < k, ldv < d,
+ * ldo < d, a null Q or K with k > 0 and nnz > 0, a null V with d > 0 and nnz > 0, or a null O with d > 0 and m > 0;
+ * CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format; CSR5HIP_UNKOWN_FORMAT before inputCSR.
+ * Single handles only: csr5hip_multi has no such call (a shard holds whole rows: call it on the shard handles). */
+int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k,
+                      const void *d_V, int ldv, int d, void *d_O, int ldo);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);

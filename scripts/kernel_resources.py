@@ -2,7 +2,7 @@
 """Resource table of the SpMV kernels from hipcc's own -Rpass-analysis=kernel-resource-usage remarks.
 
     python scripts/kernel_resources.py [--filter k_spmv] [--sigmas few|all] > profiles/rNN_resources.md
-Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
+Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
 VGPRs / SGPRs / scratch / LDS / occupancy in waves per SIMD.  Runs without a GPU."""
 import argparse
 import os
@@ -21,7 +21,7 @@ def demangle(names):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--filter", default="k_spmv|k_spmm|k_sddmm|k_row_softmax|k_slab|k_calibrate|k_range|k_x_permute|k_refresh|k_companion")
+    ap.add_argument("--filter", default="k_spmv|k_spmm|k_sddmm|k_row_softmax|k_attention|k_slab|k_calibrate|k_range|k_x_permute|k_refresh|k_companion")
     ap.add_argument("--sigmas", default="few")
     ap.add_argument("--match", default=None, help="regex on the demangled name")
     args = ap.parse_args()
@@ -30,6 +30,7 @@ def main():
                       ("csr5_spmm.hip", ["-DCSR5_SPMM_ONLY_F64"]), ("csr5_spmm.hip", ["-DCSR5_SPMM_ONLY_F32"]),
                       ("csr5_sddmm.hip", ["-DCSR5_SDDMM_ONLY_F64"]), ("csr5_sddmm.hip", ["-DCSR5_SDDMM_ONLY_F32"]),
                       ("csr5_softmax.hip", ["-DCSR5_SOFTMAX_ONLY_F64"]), ("csr5_softmax.hip", ["-DCSR5_SOFTMAX_ONLY_F32"]),
+                      ("csr5_attention.hip", ["-DCSR5_ATTENTION_ONLY_F64"]), ("csr5_attention.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
                       ("csr5_slab.hip", []), ("csr5_hot.hip", []),
                       ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F64"]), ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F32"]),
                       ("csr5_companion.hip", [])):
