@@ -29,8 +29,9 @@ where it needs them (above), so interleaved forwards and backwards on one handle
 
 ``fused_attention(A, Q, K, V)`` is the same function as ``attention`` with a one-launch forward: ``A.attention`` into
 ``torch.empty``, nothing of length nnz allocated, only Q, K and V saved, the handle's values and the record of them untouched
-(the forward of inference, under ``torch.no_grad()``, where the values in the handle belong to somebody else).  Its backward
-recomputes through ``attention`` and therefore DOES leave the handle as that function's backward does (below).
+(the forward of inference, under ``torch.no_grad()``, where the values in the handle belong to somebody else).  Its default
+backward recomputes through ``attention`` and therefore DOES leave the handle as that function's backward does (below);
+``backward="fused"`` is one ``A.attentionBackward`` call instead, which leaves the handle untouched as the forward does.
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -192,12 +193,12 @@ def attention(A, Q, K, V):
 
 class _FusedAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, A, Q, K, V):
+    def forward(ctx, A, Q, K, V, fused_backward=False):
         Qc, Kc, Vc = (_rows_unit_stride(t.detach()) for t in (Q, K, V))
         _on_current_stream(A, Qc.device)
         O = torch.empty((A._m, Vc.shape[1]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row)
         _check(A.attention(Qc, Kc, Vc, O), "attention")
-        ctx.A = A
+        ctx.A, ctx.fused_backward = A, fused_backward
         ctx.save_for_backward(Qc, Kc, Vc)
         return O
 
@@ -205,25 +206,51 @@ class _FusedAttention(torch.autograd.Function):
     def backward(ctx, dO):
         need = ctx.needs_input_grad[1:4]
         if not any(need):
-            return None, None, None, None
+            return None, None, None, None, None
+        if ctx.fused_backward:
+            return (None,) + _fused_backward(ctx.A, ctx.saved_tensors, need, dO) + (None,)
         with torch.enable_grad():
             ops = [t.detach().requires_grad_(True) if n else t for t, n in zip(ctx.saved_tensors, need)]
             out = attention(ctx.A, *ops)
             grads = iter(torch.autograd.grad(out, [t for t, n in zip(ops, need) if n], dO))
-        return (None,) + tuple(next(grads) if n else None for n in need)
+        return (None,) + tuple(next(grads) if n else None for n in need) + (None,)
 
 
-def fused_attention(A, Q, K, V):
+def _fused_backward(A, saved, need, dO):
+    """(dQ, dK, dV), None where not needed, by ONE ``A.attentionBackward`` on the current stream"""
+    Q, K, V = saved
+    dO = _rows_unit_stride(dO.detach())
+    _on_current_stream(A, dO.device)
+    outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(saved, need)]
+    work = None
+    if need[1] or need[2]:
+        if not A.info().transpose_built:
+            _check(A.buildTranspose(), "buildTranspose")
+        work = torch.empty(4 * A._m, dtype=dO.dtype, device=dO.device)
+    _check(A.attentionBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work), "attentionBackward")
+    return tuple(outs)
+
+
+def fused_attention(A, Q, K, V, backward="recompute"):
     """``attention(A, Q, K, V)`` -- the same function, the same gradients -- with the forward in ONE launch (``A.attention``): no
     scores, no weights, nothing of length nnz is allocated or written, and only Q, K and V are kept for backward.  The forward
     neither reads nor changes the handle's values and does not touch the record of them, so under ``torch.no_grad()`` the
     handle is exactly what it was.  The output agrees with ``attention``'s to rounding, not bit for bit (the normalisation
     comes after the product, and the product is summed row-wise).
 
-    Backward recomputes the weights through the existing pieces: ``attention`` on detached copies of exactly those operands
-    that need a gradient, then ``torch.autograd.grad`` with the incoming gradient, so the three gradients are bit for bit
-    those of ``attention`` for the same inputs.  The rules of that function therefore apply AFTER A BACKWARD: the handle holds
-    whatever values the last call gave it (the recomputed weights, or a gradient from ``sddmm``'s backward), and the transposed
-    companion is built (once per conversion: it allocates and synchronises) only when K or V needs a gradient.  Nothing runs
-    in backward when no input needs a gradient."""
-    return _FusedAttention.apply(A, Q, K, V)
+    ``backward="recompute"`` (the default) recomputes the weights through the existing pieces: ``attention`` on detached copies
+    of exactly those operands that need a gradient, then ``torch.autograd.grad`` with the incoming gradient, so the three
+    gradients are bit for bit those of ``attention`` for the same inputs.  The rules of that function therefore apply AFTER A
+    BACKWARD: the handle holds whatever values the last call gave it (the recomputed weights, or a gradient from ``sddmm``'s
+    backward), and the transposed companion is built (once per conversion: it allocates and synchronises) only when K or V
+    needs a gradient.
+
+    ``backward="fused"`` is ONE ``A.attentionBackward`` call (two launches) on the current stream: ``torch.empty`` outputs for
+    exactly the inputs that need a gradient, a workspace of 4 m values and the transposed companion only when K or V needs one,
+    nothing of length nnz, and the handle's values and the record of them untouched -- a handle whose values belong to somebody
+    else can be trained through.  Its gradients agree with the other route's to rounding, not bit for bit.
+
+    Nothing runs in backward when no input needs a gradient."""
+    if backward not in ("recompute", "fused"):
+        raise ValueError(f"fused_attention: backward must be 'recompute' or 'fused', not {backward!r}")
+    return _FusedAttention.apply(A, Q, K, V, backward == "fused")

@@ -61,14 +61,10 @@
 // every FMA is written out (fma_vt); nothing else may be contracted
 #pragma clang fp contract(off)
 
-namespace csr5 {
+// the row classes' constants, the rank -> storage map and the score chain: shared with csr5_attention_bwd.hip
+#include "csr5_attention_dev.h"
 
-constexpr int AT_BLOCK = 256;                      // lanes = rows of a workgroup
-constexpr int AT_WAVES = AT_BLOCK / OMEGA;
-constexpr int AT_G = 16;                           // lanes of a short row; rows up to this many entries are short
-constexpr int AT_WAVE_ROW = 512;                   // entries a wavefront stages: rows up to this length are one wavefront's
-constexpr int AT_STAGE = AT_WAVES * AT_WAVE_ROW;   // entries the workgroup stages: a hub row's chunk
-constexpr int AT_HUB_BLOCKS = 4;                   // column blocks of 64 whose accumulators a lane of a hub row holds
+namespace csr5 {
 
 template <typename VT>
 struct AttArgs {
@@ -82,76 +78,6 @@ struct AttArgs {
     VT *O;
     int ldq, ldk, ldv, ldo;
 };
-
-// storage position of the entry of rank j inside a row whose first entry has CSR rank t0 * T + rem0
-template <typename VT>
-__device__ __forceinline__ size_t att_storage(const AttArgs<VT> &A, const int t0, const int rem0, const int j)
-{
-    unsigned x = (unsigned)rem0 + (unsigned)j;
-    int t = t0;
-    if (x >= (unsigned)A.T) {
-        const unsigned q = x / (unsigned)A.T;
-        t += (int)q;
-        x -= q * (unsigned)A.T;
-    }
-    const size_t base = (size_t)t * A.T;
-    if (t >= A.tiles || A.tile_ptr[t] == A.tile_ptr[t + 1])
-        return base + x; // CSR tail / fast-track tile: CSR order
-    const unsigned l = (x * A.recip) >> 20; // x / sigma: exact for x < 2 048, sigma <= 32
-    const unsigned i = x - l * (unsigned)A.sigma;
-    return base + (size_t)i * OMEGA + l;
-}
-
-template <typename VT>
-__device__ __forceinline__ void att_load16(const VT *__restrict__ p, VT *o)
-{
-    const uint4 w = *reinterpret_cast<const uint4 *>(p);
-    if constexpr (sizeof(VT) == 8) {
-        o[0] = __builtin_bit_cast(double, (unsigned long long)w.y << 32 | w.x);
-        o[1] = __builtin_bit_cast(double, (unsigned long long)w.w << 32 | w.z);
-    } else {
-        o[0] = __builtin_bit_cast(float, w.x);
-        o[1] = __builtin_bit_cast(float, w.y);
-        o[2] = __builtin_bit_cast(float, w.z);
-        o[3] = __builtin_bit_cast(float, w.w);
-    }
-}
-
-// the chain of the definition over one row of Q and one of K.  VEC: blocks of 32 bytes by 16-byte loads, the rest by elements.
-template <typename VT, bool VEC>
-__device__ __forceinline__ VT att_score(const VT *__restrict__ q, const VT *__restrict__ kr, const int k)
-{
-    constexpr int PER = 16 / (int)sizeof(VT);
-    VT acc = (VT)0;
-    int c = 0;
-    if constexpr (VEC) {
-        for (; c + 2 * PER <= k; c += 2 * PER) {
-            VT a[2 * PER], b[2 * PER];
-            att_load16<VT>(q + c, a);
-            att_load16<VT>(q + c + PER, a + PER);
-            att_load16<VT>(kr + c, b);
-            att_load16<VT>(kr + c + PER, b + PER);
-#pragma unroll
-            for (int j = 0; j < 2 * PER; j++)
-                acc = fma_vt(a[j], b[j], acc);
-        }
-    }
-#pragma unroll 4
-    for (; c < k; c++)
-        acc = fma_vt(q[c], kr[c], acc);
-    return acc;
-}
-
-// LDS written by some lanes of a wavefront is read by others of the same wavefront
-__device__ __forceinline__ void att_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the smallest power of two >= w, 1 <= w <= 64
-__device__ __forceinline__ int att_pow2(const int w) { return w <= 1 ? 1 : 1 << (32 - __builtin_clz((unsigned)(w - 1))); }
 
 // ---- rows of at most 16 entries (empty rows included): 16 lanes per row, 4 rows of the wavefront per pass ------------------
 template <typename VT, bool VEC>

@@ -1,0 +1,547 @@
+// csr5_attention_bwd.hip -- the gradients of csr5_attention.hip's O for Q, K and V in TWO launches, for gfx950 (wave64), with
+// nothing of length nnz written or read back and the handle's values untouched.  dO is the gradient arriving for O (m x d).
+//
+// DEFINITION per stored entry e = (i, j), every operation its own rounding (fp contract(off), the FMAs written out):
+//     s_e  = the forward's chain fma(Q[i, k-1], K[j, k-1], ... fma(Q[i, 0], K[j, 0], +0) ...), the same bits
+//     M_i  = the exact maximum of row i's scores,  w_e = exp(s_e - M_i),  Z_i = sum of the row's w by the forward's tree
+//     r_i  = 1 / Z_i,  p_e = w_e * r_i                                           (csr5hip_row_softmax's bits)
+//     dp_e = fma(dO[i, d-1], V[j, d-1], ... fma(dO[i, 0], V[j, 0], +0) ...)     (csr5hip_sddmm's chain)
+//     D_i  = sum over the row of round(p_e * dp_e) by Z's tree,  ds_e = p_e * (dp_e - D_i)   (csr5hip_row_softmax_grad's bits)
+//     dQ[i, c] = sum_e ds_e K[j_e, c]       dK[j, c] = sum_e ds_e Q[i_e, c]       dV[j, c] = sum_e p_e dO[i_e, c]
+//
+// THE ROW KERNEL walks the parent's pattern (row_ptr, tile_ptr, tile-ordered column_index) with the forward's row classes: it
+// computes M, r and D of every row, writes them to the workspace (4 values per row: M, r, D, one unused) when one is given, and
+// writes dQ when it is wanted.  THE COLUMN KERNEL walks the transposed companion's pattern -- row j of A^T lists the rows i_e of
+// the entries of column j in A's CSR order --, with the same classes decided by the column's length: per entry it gathers M, r
+// and D of row i_e, recomputes s_e and dp_e by the chains above and p_e and ds_e by the formulas above -- so an entry has the
+// same p and ds on both sides --, and writes dV and dK.  No floating-point atomics, no scratch; each kernel reads row_ptr,
+// tile_ptr and column_index of its handle and nothing else of it.
+//
+// EVERY row of a wanted output is written in its k (d) columns, a row (column) of the matrix without entries with +0; nothing is
+// written beyond.  A row beyond 2 048 entries recomputes its scores per sweep, as the forward does.
+//
+// THE SUMMATION ORDER.  Z and D: the forward's Z (csr5_attention.hip), a function of the row's length.  Every accumulation is
+// the forward's acc_c rule as a function of (L, width) alone: dQ with (row length, k), dK with (column length, k), dV with
+// (column length, d).  So the bits of a row of dQ depend only on that row's operands, those of a row of dK or dV only on its
+// column's entries in CSR order and those rows' operands: not on sigma (the parent's or the companion's), any option, leading
+// dimensions, alignment (16-byte loads only where every row of all four operands is 16-byte aligned; they feed the same chains)
+// or the run.
+//
+// NON-FINITE values: a row whose forward output is NaN (Z = NaN) has r = NaN, so p and ds are NaN in all its entries: NaN in its
+// dQ row and in the dK and dV rows of exactly the columns it stores.  A -Inf score has p = +0 * r = +0.
+#include "csr5_internal.h"
+#include "csr5_wave.h"
+
+#include <math.h>
+
+// every FMA is written out (fma_vt); nothing else may be contracted
+#pragma clang fp contract(off)
+
+#include "csr5_attention_dev.h"
+
+namespace csr5 {
+
+template <typename VT>
+struct AttBwdArgs {
+    int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
+    int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
+    unsigned recip;
+    const int32_t *row_ptr;
+    const int32_t *col;
+    const uint32_t *tile_ptr;
+    const VT *Q, *K, *V, *dO;
+    VT *dQ, *dK, *dV; // row kernel: dQ or null; column kernel: dK, dV, one of them may be null
+    VT *work;         // [4 m]: M, r, D and one unused value per row of A; the row kernel writes (null: not wanted), the column kernel reads
+    int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
+};
+
+// s_e and dp_e of the entry (i, j)
+template <typename VT, bool VEC>
+__device__ __forceinline__ void bwd_entry(const AttBwdArgs<VT> &A, const size_t i, const size_t j, VT &s, VT &dp)
+{
+    s = att_score<VT, VEC>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
+    dp = att_score<VT, VEC>(A.dO + i * A.lddo, A.V + j * A.ldv, A.d);
+}
+
+// p_e and ds_e of the entry (i, j) from the workspace values of row i: the column kernel's entry
+template <typename VT, bool VEC>
+__device__ __forceinline__ void bwd_entry_col(const AttBwdArgs<VT> &A, const size_t i, const size_t j, VT &p, VT &ds)
+{
+    const VT M = A.work[4 * i], r = A.work[4 * i + 1], D = A.work[4 * i + 2];
+    VT s, dp;
+    bwd_entry<VT, VEC>(A, i, j, s, dp);
+    p = exp_vt(s - M) * r;
+    ds = p * (dp - D);
+}
+
+// ---- accumulation, L <= 16: ONE chain per output column over the entries in ascending order.  coef / idx: lane sub * 16 + e
+// holds the coefficient and the operand row of entry e; out: the output row (used where rowok)
+template <typename VT>
+__device__ __forceinline__ void bwd_short_acc(const bool rowok, const int rl, const int sub, const int pos, const VT coef, const int idx,
+                                              const VT *__restrict__ X, const int ldx, const int width, VT *out)
+{
+    constexpr int G = AT_G;
+    for (int cb = 0; cb < width; cb += G) { // (uniform)
+        const int c = cb + pos;
+        VT acc = (VT)0;
+        for (int e = 0; e < G; e++) {
+            if (!__any(rowok && e < rl)) // (uniform: the shuffles below are executed by every lane)
+                break;
+            const VT we = __shfl(coef, sub * G + e, OMEGA);
+            const int je = __shfl(idx, sub * G + e, OMEGA);
+            if (rowok && e < rl && c < width)
+                acc = fma_vt(we, X[(size_t)(uint32_t)je * ldx + c], acc);
+        }
+        if (rowok && c < width)
+            out[c] = acc;
+    }
+}
+
+// ---- accumulation, 17 <= L <= 512: the forward's wavefront rule; coef / idx: the wavefront's staged entries in LDS
+template <typename VT>
+__device__ __forceinline__ void bwd_wave_acc(const VT *coef, const int *idx, const int rl, const VT *__restrict__ X, const int ldx,
+                                             const int width, VT *out)
+{
+    const int lane = threadIdx.x & (OMEGA - 1);
+    for (int cb = 0; cb < width; cb += OMEGA) {
+        const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+        const int C = att_pow2(wb), S = OMEGA / C;
+        const int slot = lane / C, cc = lane & (C - 1);
+        VT acc = (VT)0;
+        if (cc < wb) {
+            const VT *x = X + cb + cc;
+#pragma unroll 4
+            for (int e = slot; e < rl; e += S)
+                acc = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], acc);
+        }
+        for (int off = C; off < OMEGA; off <<= 1) // (uniform; adjacent slots first)
+            acc += __shfl_xor(acc, off, OMEGA);
+        if (slot == 0 && cc < wb)
+            out[cb + cc] = acc;
+    }
+}
+
+// ---- accumulation, L > 512: the forward's workgroup rule.  staged: coef / idx hold all rl entries (filled by the caller; the
+// barrier below publishes them); otherwise fill(base, n) writes entries base .. base + n - 1 to coef / idx [0, n) chunk by chunk,
+// again for every 256 output columns.  Ends with a barrier: the stage is free.
+template <typename VT, typename FILL>
+__device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FILL fill, const VT *coef, const int *idx,
+                                            const VT *__restrict__ X, const int ldx, const int width, VT *out, VT *red)
+{
+    const int tid = (int)threadIdx.x;
+    for (int cg = 0; cg < width; cg += OMEGA * AT_HUB_BLOCKS) {
+        VT acc[AT_HUB_BLOCKS];
+#pragma unroll
+        for (int b = 0; b < AT_HUB_BLOCKS; b++)
+            acc[b] = (VT)0;
+        for (int base = 0; base < rl; base += AT_STAGE) {
+            const int n = rl - base < AT_STAGE ? rl - base : AT_STAGE;
+            if (!staged) {
+                __syncthreads(); // (the stage is free: the previous chunk has been read)
+                fill(base, n);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int b = 0; b < AT_HUB_BLOCKS; b++) {
+                const int cb = cg + b * OMEGA;
+                if (cb < width) {
+                    const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+                    const int C = att_pow2(wb), S = AT_BLOCK / C; // (AT_STAGE is a multiple of S: a chunk keeps j mod S)
+                    const int slot = tid / C, cc = tid & (C - 1);
+                    if (cc < wb) {
+                        const VT *x = X + cb + cc;
+                        VT o = acc[b];
+#pragma unroll 4
+                        for (int e = slot; e < n; e += S)
+                            o = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], o);
+                        acc[b] = o;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < AT_HUB_BLOCKS; b++) {
+            const int cb = cg + b * OMEGA;
+            if (cb < width) { // (uniform)
+                const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+                const int C = att_pow2(wb);
+                VT o = acc[b];
+                for (int off = C; off < OMEGA; off <<= 1) // adjacent slots of the wavefront first ...
+                    o += __shfl_xor(o, off, OMEGA);
+                red[tid] = o;
+                __syncthreads();
+                if (tid < wb) // ... then (w0 + w1) + (w2 + w3); lane c < C of every wavefront holds column c
+                    out[cb + tid] = (red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid]);
+                __syncthreads(); // (red is free for the next block)
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// ---- lines of at most 16 entries (empty ones included): 16 lanes per line, 4 lines of the wavefront per pass ---------------
+template <typename VT, bool VEC, bool COL>
+__device__ __forceinline__ void bwd_short(const AttBwdArgs<VT> &A, const long long row0, const int len, const int t0, const int rem0)
+{
+    constexpr int G = AT_G, ROWS = OMEGA / G;
+    const int lane = threadIdx.x & (OMEGA - 1);
+    const int sub = lane / G, pos = lane % G;
+    const unsigned long long cls = __ballot(len >= 0 && len <= G); // (len = -1: no such line)
+    if (!cls)
+        return;
+    for (int pass = 0; pass < G; pass++) {
+        const unsigned long long here = (cls >> (pass * ROWS)) & ((1ull << ROWS) - 1);
+        if (!here) // (wave-uniform)
+            continue;
+        const int src = pass * ROWS + sub;
+        const int rl = __shfl(len, src, OMEGA);
+        const int rt0 = __shfl(t0, src, OMEGA);
+        const int rrem = __shfl(rem0, src, OMEGA);
+        const bool rowok = (cls >> src) & 1;
+        const bool act = rowok && pos < rl;
+        const size_t r = (size_t)(row0 + src);
+        int other = 0;
+        if constexpr (COL) {
+            VT p = (VT)0, ds = (VT)0;
+            if (act) {
+                other = A.col[att_storage(A, rt0, rrem, pos)];
+                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, p, ds);
+            }
+            if (A.dV)
+                bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
+            if (A.dK)
+                bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
+        } else {
+            VT s = neg_inf<VT>(), dp = (VT)0;
+            if (act) {
+                other = A.col[att_storage(A, rt0, rrem, pos)];
+                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, s, dp);
+            }
+            const VT mx = group_max<G>(s);
+            const VT w = act ? exp_vt(s - mx) : (VT)0;
+            const VT rinv = (VT)1 / group_sum<G>(w);
+            const VT p = act ? w * rinv : (VT)0;
+            const VT pg = p * dp;
+            const VT D = group_sum<G>(act ? pg : (VT)0);
+            const VT ds = act ? p * (dp - D) : (VT)0;
+            if (A.work && rowok && pos == 0) {
+                A.work[4 * r] = mx;
+                A.work[4 * r + 1] = rinv;
+                A.work[4 * r + 2] = D;
+            }
+            if (A.dQ)
+                bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
+        }
+    }
+}
+
+// ---- a line of 17 .. 512 entries: one wavefront; a / b / cl: the wavefront's 512 staged values, values and indices ---------
+template <typename VT, bool VEC, bool COL>
+__device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
+                                              VT *b, int *cl)
+{
+    const int lane = threadIdx.x & (OMEGA - 1);
+    if constexpr (COL) {
+        for (int j = lane; j < rl; j += OMEGA) {
+            const int i = A.col[att_storage(A, t0, rem0, j)];
+            VT p, ds;
+            bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
+            a[j] = p;
+            b[j] = ds;
+            cl[j] = i;
+        }
+        att_wave_sync();
+        if (A.dV)
+            bwd_wave_acc<VT>(a, cl, rl, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
+        if (A.dK)
+            bwd_wave_acc<VT>(b, cl, rl, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
+    } else {
+        VT mx = neg_inf<VT>();
+        for (int j = lane; j < rl; j += OMEGA) {
+            const int cj = A.col[att_storage(A, t0, rem0, j)];
+            VT s, dp;
+            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
+            a[j] = s;
+            b[j] = dp;
+            cl[j] = cj;
+            mx = max_vt(mx, s);
+        }
+        mx = wave_max(mx);
+        VT z = (VT)0;
+        for (int j = lane; j < rl; j += OMEGA) { // (a lane reads back what it stored itself, here and below)
+            const VT w = exp_vt(a[j] - mx);
+            a[j] = w;
+            z += w;
+        }
+        const VT rinv = (VT)1 / wave_sum(z);
+        VT dsum = (VT)0;
+        for (int j = lane; j < rl; j += OMEGA) {
+            const VT p = a[j] * rinv;
+            const VT pg = p * b[j];
+            a[j] = p;
+            dsum += pg;
+        }
+        const VT D = wave_sum(dsum);
+        for (int j = lane; j < rl; j += OMEGA)
+            a[j] = a[j] * (b[j] - D);
+        if (A.work && lane == 0) {
+            A.work[4 * r] = mx;
+            A.work[4 * r + 1] = rinv;
+            A.work[4 * r + 2] = D;
+        }
+        att_wave_sync();
+        if (A.dQ)
+            bwd_wave_acc<VT>(a, cl, rl, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
+    }
+    att_wave_sync(); // (the next line's entries stay behind these reads)
+}
+
+// ---- a line beyond 512 entries: the workgroup; a / b / cl: the AT_STAGE staged entries, red: AT_BLOCK values, red4: AT_WAVES
+template <typename VT, bool VEC, bool COL>
+__device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
+                                             VT *b, int *cl, VT *red, VT *red4)
+{
+    const int tid = (int)threadIdx.x;
+    const bool staged = rl <= AT_STAGE; // (uniform over the workgroup, as every loop bound and barrier below)
+    if constexpr (COL) {
+        auto fill = [&](const int base, const int n) {
+            for (int jj = tid; jj < n; jj += AT_BLOCK) {
+                const int i = A.col[att_storage(A, t0, rem0, base + jj)];
+                VT p, ds;
+                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
+                a[jj] = p;
+                b[jj] = ds;
+                cl[jj] = i;
+            }
+        };
+        if (staged)
+            fill(0, rl);
+        if (A.dV)
+            bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.dO, A.lddo, A.d, A.dV + r * A.lddv, red);
+        if (A.dK)
+            bwd_hub_acc<VT>(rl, staged, fill, b, cl, A.Q, A.ldq, A.k, A.dK + r * A.lddk, red);
+    } else {
+        VT mx = neg_inf<VT>();
+        for (int j = tid; j < rl; j += AT_BLOCK) {
+            const int cj = A.col[att_storage(A, t0, rem0, j)];
+            VT s, dp;
+            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
+            if (staged) {
+                a[j] = s;
+                b[j] = dp;
+                cl[j] = cj;
+            }
+            mx = max_vt(mx, s);
+        }
+        mx = block_combine<VT, true>(wave_max(mx), red4);
+        VT z = (VT)0;
+        for (int j = tid; j < rl; j += AT_BLOCK) { // (a lane reads back what it stored itself, here and below)
+            VT s;
+            if (staged) {
+                s = a[j];
+            } else {
+                const int cj = A.col[att_storage(A, t0, rem0, j)];
+                s = att_score<VT, VEC>(A.Q + r * A.ldq, A.K + (size_t)(uint32_t)cj * A.ldk, A.k);
+            }
+            const VT w = exp_vt(s - mx);
+            if (staged)
+                a[j] = w;
+            z += w;
+        }
+        const VT rinv = (VT)1 / block_combine<VT, false>(wave_sum(z), red4);
+        VT dsum = (VT)0;
+        for (int j = tid; j < rl; j += AT_BLOCK) {
+            VT w, dp;
+            if (staged) {
+                w = a[j];
+                dp = b[j];
+            } else {
+                const int cj = A.col[att_storage(A, t0, rem0, j)];
+                VT s;
+                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
+                w = exp_vt(s - mx);
+            }
+            const VT p = w * rinv;
+            const VT pg = p * dp;
+            if (staged)
+                a[j] = p;
+            dsum += pg;
+        }
+        const VT D = block_combine<VT, false>(wave_sum(dsum), red4);
+        if (staged)
+            for (int j = tid; j < rl; j += AT_BLOCK)
+                a[j] = a[j] * (b[j] - D);
+        if (A.work && tid == 0) {
+            A.work[4 * r] = mx;
+            A.work[4 * r + 1] = rinv;
+            A.work[4 * r + 2] = D;
+        }
+        auto fill = [&](const int base, const int n) {
+            for (int jj = tid; jj < n; jj += AT_BLOCK) {
+                const int cj = A.col[att_storage(A, t0, rem0, base + jj)];
+                VT s, dp;
+                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
+                const VT p = exp_vt(s - mx) * rinv;
+                a[jj] = p * (dp - D);
+                cl[jj] = cj;
+            }
+        };
+        if (A.dQ)
+            bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.K, A.ldk, A.k, A.dQ + r * A.lddq, red);
+        else
+            __syncthreads(); // (the stage is free for the next hub line)
+    }
+}
+
+template <typename VT, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT> A)
+{
+    __shared__ VT a[AT_STAGE];
+    __shared__ VT b[AT_STAGE];
+    __shared__ int cl[AT_STAGE];
+    __shared__ VT red[AT_BLOCK];
+    __shared__ VT red4[AT_WAVES];
+    __shared__ int hub_n;
+    __shared__ int hub_row[AT_BLOCK];
+    if (threadIdx.x == 0)
+        hub_n = 0;
+    __syncthreads();
+
+    const int wave = (int)(threadIdx.x >> 6);
+    const long long row0 = (long long)blockIdx.x * AT_BLOCK + wave * OMEGA; // the wavefront's first line
+    const long long r = (long long)blockIdx.x * AT_BLOCK + threadIdx.x;
+    int first = 0, len = -1, t0 = 0, rem0 = 0;
+    if (r < A.lines) {
+        first = A.row_ptr[r];
+        len = A.row_ptr[r + 1] - first;
+        len = len < 0 ? 0 : len;
+        t0 = (int)((unsigned)first / (unsigned)A.T);
+        rem0 = first - t0 * A.T;
+    }
+    bwd_short<VT, VEC, COL>(A, row0, len, t0, rem0);
+
+    unsigned long long todo = __ballot(len > AT_G && len <= AT_WAVE_ROW);
+    while (todo) {
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        bwd_wave_line<VT, VEC, COL>(A, (size_t)(row0 + src), __builtin_amdgcn_readlane(len, src), __builtin_amdgcn_readlane(t0, src),
+                                    __builtin_amdgcn_readlane(rem0, src), a + wave * AT_WAVE_ROW, b + wave * AT_WAVE_ROW,
+                                    cl + wave * AT_WAVE_ROW);
+    }
+
+    if (len > AT_WAVE_ROW)
+        hub_row[atomicAdd(&hub_n, 1)] = (int)threadIdx.x; // (an integer counter in LDS: the order of the list decides no bit)
+    __syncthreads(); // (and every wavefront is done with its share of the stage)
+    const int hubs = __builtin_amdgcn_readfirstlane(hub_n);
+    for (int i = 0; i < hubs; i++) { // (uniform over the workgroup: the barriers inside are reached by all)
+        const long long hr = (long long)blockIdx.x * AT_BLOCK + __builtin_amdgcn_readfirstlane(hub_row[i]);
+        const int ra = __builtin_amdgcn_readfirstlane(A.row_ptr[hr]);
+        const int rl = __builtin_amdgcn_readfirstlane(A.row_ptr[hr + 1]) - ra;
+        const int ht0 = (int)((unsigned)ra / (unsigned)A.T);
+        bwd_hub_line<VT, VEC, COL>(A, (size_t)hr, rl, ht0, ra - ht0 * A.T, a, b, cl, red, red4);
+    }
+}
+
+template <typename VT, bool COL>
+static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, AttBwdArgs<VT> A, const bool vec, hipStream_t s)
+{
+    if (g.m <= 0)
+        return hipSuccess;
+    A.lines = g.m;
+    A.sigma = g.sigma > 0 ? g.sigma : 1;
+    A.T = g.tile_elems > 0 ? g.tile_elems : OMEGA;
+    A.tiles = g.p > 1 ? g.p - 1 : 0;
+    A.recip = (1u << 20) / (unsigned)A.sigma + 1u;
+    A.row_ptr = d.row_ptr;
+    A.col = d.col;
+    A.tile_ptr = d.tile_ptr;
+    const dim3 grid((unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK)), block(AT_BLOCK);
+    if (vec)
+        hipLaunchKernelGGL((k_attention_bwd<VT, true, COL>), grid, block, 0, s, A);
+    else
+        hipLaunchKernelGGL((k_attention_bwd<VT, false, COL>), grid, block, 0, s, A);
+    return hipGetLastError();
+}
+
+// g / d: the parent's pattern (the row kernel); gt / dt: the transposed companion's (the column kernel, only when dK or dV is
+// wanted: null otherwise).  The row kernel runs when dQ is wanted or the column kernel needs the workspace.
+template <typename VT>
+static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
+                                      int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
+                                      void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+{
+    AttBwdArgs<VT> A{};
+    A.k = k;
+    A.d = dcols;
+    A.Q = (const VT *)Q;
+    A.K = (const VT *)K;
+    A.V = (const VT *)V;
+    A.dO = (const VT *)dO;
+    A.ldq = ldq;
+    A.ldk = ldk;
+    A.ldv = ldv;
+    A.lddo = lddo;
+    A.lddq = lddq;
+    A.lddk = lddk;
+    A.lddv = lddv;
+    // 16-byte loads: every row of Q, K, V and dO starts on a 16-byte boundary (a chain shorter than one block of 32 bytes takes
+    // element loads anyway)
+    bool vec = true;
+    const void *ptrs[4] = {Q, K, V, dO};
+    const int lds[4] = {ldq, ldk, ldv, lddo};
+    for (int i = 0; i < 4; i++)
+        vec = vec && reinterpret_cast<uintptr_t>(ptrs[i]) % 16 == 0 && ((size_t)lds[i] * sizeof(VT)) % 16 == 0;
+    const bool column = gt && dt && (dK || dV);
+    hipError_t e = hipSuccess;
+    if (dQ || column) {
+        AttBwdArgs<VT> R = A;
+        R.dQ = k > 0 ? (VT *)dQ : nullptr;
+        R.work = column ? (VT *)work : nullptr;
+        if (R.dQ || R.work)
+            e = attention_bwd_side<VT, false>(g, d, R, vec, s);
+    }
+    if (e == hipSuccess && column) {
+        AttBwdArgs<VT> C = A;
+        C.dK = k > 0 ? (VT *)dK : nullptr;
+        C.dV = dcols > 0 ? (VT *)dV : nullptr;
+        C.work = (VT *)work;
+        if (C.dK || C.dV)
+            e = attention_bwd_side<VT, true>(*gt, *dt, C, vec, s);
+    }
+    return e;
+}
+
+// The product build compiles this file once per value type (-DCSR5_ATTENTION_BWD_ONLY_F64 / _F32), as csr5_attention.hip.
+#if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
+hipError_t launch_attention_bwd_f64(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
+                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
+                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+{
+    return attention_bwd_typed<double>(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+}
+#endif
+#if !defined(CSR5_ATTENTION_BWD_ONLY_F64)
+hipError_t launch_attention_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
+                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
+                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+{
+    return attention_bwd_typed<float>(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+}
+#endif
+
+#if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
+hipError_t launch_attention_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
+                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
+                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
+
+hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
+                                const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
+                                int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+{
+    return value_type == CSR5HIP_F64
+               ? launch_attention_bwd_f64(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s)
+               : launch_attention_bwd_f32(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+}
+#endif
+
+} // namespace csr5

@@ -1732,6 +1732,44 @@ int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_
     return CSR5HIP_SUCCESS;
 }
 
+// dQ, dK, dV of csr5hip_attention in two launches (csr5_attention_bwd.hip): the row kernel on the parent's pattern, the column kernel on
+// the transposed companion's.  Allocates nothing, changes nothing of the handle or of its companion: enqueue-only.
+int csr5hip_attention_backward(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv,
+                               int d, const void *d_dO, int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv,
+                               void *d_work)
+{
+    if (!h || k < 0 || d < 0 || ldq < k || ldk < k || lddq < k || lddk < k || ldv < d || lddo < d || lddv < d)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
+    const bool any = d_dQ || column;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (column && !h->at_built) {
+        g_last_error = "csr5hip_attention_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (!any)
+        return CSR5HIP_SUCCESS;
+    const size_t vs = h->vsize();
+    if (nnz == 0 || (column && !h->at)) { // no entries (and then no companion arrays): the zeros
+        if (d_dQ && k > 0 && h->g.m > 0)
+            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)k * vs, (size_t)h->g.m, h->stream));
+        if (d_dK && k > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)k * vs, (size_t)h->g.n, h->stream));
+        if (d_dV && d > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)d * vs, (size_t)h->g.n, h->stream));
+        return CSR5HIP_SUCCESS;
+    }
+    HIP_TRY(launch_attention_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr, h->value_type, d_Q, ldq, d_K, ldk,
+                                 k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

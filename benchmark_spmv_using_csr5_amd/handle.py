@@ -257,6 +257,71 @@ class anonymouslibHandle:
         return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
                                            _ptr(O), int(ldo))
 
+    # -- the gradients of attention in two launches (csr5hip.h csr5hip_attention_backward) -----------
+    def attentionBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
+        """The gradients of ``attention``'s O for Q, K and V from the gradient dO (m, d) arriving for O: dQ (m, k), dK (n, k) and
+        dV (n, d), each written in EVERY row (rows and columns of the matrix without entries with +0, so they may be
+        ``torch.empty``) or None when not wanted.  Operands as ``attention``'s (stride(1) == 1, leading dimension stride(0)); an
+        output shares storage with no input, no other output and not with ``work``.  dK and dV need ``work``, a contiguous 1-D
+        tensor of at least 4 m values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
+        Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything else raises ValueError
+        before the library is called."""
+        who = "attentionBackward"
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        for name, t, rows, width in ins + outs:  # (the checks of attention's operands; the device comes last)
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"{who}: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 2 or t.shape[0] != rows:
+                raise ValueError(f"{who}: {name} must have shape ({rows}, {width}), not {tuple(t.shape)}")
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError(f"{who}: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < {width} = {t.shape[1]})")
+        k, d = int(Q.shape[1]), int(V.shape[1])
+        for name, t, _, width in ins[1:] + outs:
+            want = k if width == "k" else d
+            if t.shape[1] != want:
+                first = "Q" if width == "k" else "V"
+                raise ValueError(f"{who}: {first} has {want} columns, {name} {t.shape[1]}")
+        column = dK is not None or dV is not None
+        if work is not None or column:
+            if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
+                raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
+            if str(work.dtype) != dt:
+                raise ValueError(f"{who}: work has dtype {work.dtype}, the handle holds {dt}")
+            if work.dim() != 1 or work.shape[0] < 4 * self._m:
+                raise ValueError(f"{who}: work must have shape ({4 * self._m},) or longer, not {tuple(work.shape)}")
+            if not work.is_contiguous():
+                raise ValueError(f"{who}: work must be contiguous, not stride {work.stride()}")
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        scratch = (("work", work, 0, ""),) if work is not None else ()
+        for i, (oname, o, _, _) in enumerate(outs):
+            for name, t, _, _ in ins + outs[:i] + scratch:
+                if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                    raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
+        for name, t, _, _ in ins + outs + scratch:
+            if t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        if any(t.device != Q.device for _, t, _, _ in ins + outs + scratch):
+            raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t, _, _ in ins + outs + scratch))
+
+        def ld(t):
+            return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+        return self.attention_backward_ptr(Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ, ld(dQ) if dQ is not None else k,
+                                           dK, ld(dK) if dK is not None else k, dV, ld(dV) if dV is not None else d, work)
+
+    def attention_backward_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int,
+                               dV, lddv: int, work) -> int:
+        """csr5hip_attention_backward on raw device pointers (or tensors); None for an output that is not wanted"""
+        return self._lib.csr5hip_attention_backward(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                                    _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv),
+                                                    _ptr(work))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

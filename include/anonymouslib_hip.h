@@ -164,6 +164,17 @@ public:
         return _h ? csr5hip_attention(_h, (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d, (void *)O, ldo)
                   : _err;
     }
+    // extension: the gradients of attention's O for Q, K and V in two launches: dO m x d (lddo) in; dQ m x k, dK n x k, dV n x d out,
+    // any of them null when not wanted, every row of a wanted one written; work: 4 m values of scratch, needed (as the transposed
+    // companion, buildTranspose) only for dK or dV; the handle untouched (csr5hip_attention_backward)
+    int attentionBackward(const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv,
+                          int d, const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk,
+                          ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work)
+    {
+        return _h ? csr5hip_attention_backward(_h, (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d,
+                                               (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk, (void *)dV, lddv, (void *)work)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

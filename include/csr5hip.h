@@ -378,6 +378,35 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
  * Single handles only: csr5hip_multi has no such call (a shard holds whole rows: call it on the shard handles). */
 int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k,
                       const void *d_V, int ldv, int d, void *d_O, int ldo);
+/* Extension (not in the reference): the gradients of csr5hip_attention's O for Q, K and V in TWO launches, with nothing of length nnz
+ * written and the handle untouched.  d_dO is the gradient arriving for O (m x d, lddo >= d).  Per stored entry e = (i, j):
+ *     p_e  = exp(s_e - M_i) * r_i   (s_e, M_i, Z_i as in csr5hip_attention, r_i = 1 / Z_i: csr5hip_row_softmax's bits)
+ *     dp_e = sum_{c < d} dO[i, c] * V[j, c]   (csr5hip_sddmm's chain: d fused multiply-adds in ascending column order onto +0)
+ *     D_i  = sum over row i of round(p_e * dp_e) by Z's tree,   ds_e = p_e * (dp_e - D_i)   (csr5hip_row_softmax_grad's bits)
+ *     dQ[i, c] = sum_e ds_e K[j_e, c]  (m x k)    dK[j, c] = sum_e ds_e Q[i_e, c]  (n x k)    dV[j, c] = sum_e p_e dO[i_e, c]  (n x d)
+ * ANY OUTPUT MAY BE NULL: it is not wanted; with all three null the call is a successful no-op.  EVERY row of a wanted output is
+ * written in its k (d) columns -- a row or column of the matrix without entries gets +0 -- and nothing beyond them, so the outputs
+ * may be uninitialised memory.  Outputs must not overlap the inputs, each other, the workspace or any array of the handle.
+ * d_work: caller-owned scratch of 4 * m values of the handle's type (layout private: per row M, r, D and one unused value); needed
+ * only when dK or dV is wanted.  dK or dV REQUIRES THE TRANSPOSED COMPANION (csr5hip_build_transpose; never built lazily): the row
+ * kernel walks the parent's pattern, writes dQ and the workspace; the column kernel walks the companion's pattern, gathers the
+ * workspace values of every entry's row, recomputes s_e and dp_e and writes dK and dV.  dQ alone needs neither.
+ * The call allocates nothing, reads nothing back, only enqueues on the handle's stream from the first call on (capturable), and
+ * neither reads nor changes the handle's values, x, options, csr5hip_info or device_bytes.
+ * SUMMATION ORDER: every accumulation is csr5hip_attention's acc_c rule as a function of (L, width) alone: dQ with (row length, k),
+ * dK with (column length, k), dV with (column length, d); a column's entries are taken in A's CSR order.  DETERMINISM: the bits of
+ * a row of dQ depend only on that row's operands, those of a row of dK or dV only on its column's entries and those rows'
+ * operands: not on sigma (the parent's or the companion's), any option, leading dimensions, pointer alignment or the run.
+ * NON-FINITE: a row whose forward output is NaN gives NaN in its dQ row and in the dK and dV rows of exactly the columns it stores;
+ * every other output row is unaffected; a -Inf score has p = +0.
+ * Returns, decided on the host in this order: CSR5HIP_INVALID_ARGUMENT for a null handle, k < 0, d < 0 or a leading dimension below
+ * its width (ldq, ldk, lddq, lddk < k; ldv, lddo, lddv < d); CSR5HIP_INVALID_ARGUMENT, when an output is wanted and nnz > 0, for a
+ * null Q or K with k > 0, a null V or dO with d > 0, or a null workspace with dK or dV wanted; CSR5HIP_INVALID_ARGUMENT with a
+ * csr5hip_last_error text when dK or dV is wanted and there is no companion; CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format;
+ * CSR5HIP_UNKOWN_FORMAT before inputCSR.  nnz = 0 only writes the zeros.  Single handles only. */
+int csr5hip_attention_backward(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k,
+                               const void *d_V, int ldv, int d, const void *d_dO, int lddo,
+                               void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
