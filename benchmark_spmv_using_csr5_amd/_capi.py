@@ -129,6 +129,11 @@ SYMBOLS = [
     ("csr5hip_attention_backward", C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p]),
+    ("csr5hip_mha", C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                              C.c_void_p, C.c_int]),
+    ("csr5hip_mha_backward", C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p]),
     ("csr5hip_row_softmax", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("csr5hip_row_softmax_grad", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csr5hip_spmv_repeat", C.c_int, [_H, C.c_double, C.c_void_p, C.c_int]),

@@ -33,6 +33,9 @@ where it needs them (above), so interleaved forwards and backwards on one handle
 backward recomputes through ``attention`` and therefore DOES leave the handle as that function's backward does (below);
 ``backward="fused"`` is one ``A.attentionBackward`` call instead, which leaves the handle untouched as the forward does.
 
+``multihead_attention(A, Q, K, V)`` is ``fused_attention(..., backward="fused")`` for H heads at once on packed operands
+(rows, H, width): one ``A.mha`` forward, one ``A.mhaBackward`` backward, the handle untouched by both.
+
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
 """
@@ -42,7 +45,7 @@ import torch
 
 from . import _capi
 
-__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention"]
+__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention"]
 
 
 def _check(rc: int, what: str) -> None:
@@ -254,3 +257,53 @@ def fused_attention(A, Q, K, V, backward="recompute"):
     if backward not in ("recompute", "fused"):
         raise ValueError(f"fused_attention: backward must be 'recompute' or 'fused', not {backward!r}")
     return _FusedAttention.apply(A, Q, K, V, backward == "fused")
+
+
+def _packed(t):
+    """what mha takes: (rows, heads, width) with stride(2) == 1, stride(1) == width and non-overlapping rows; anything else is
+    made contiguous"""
+    if (t.dim() == 3 and (t.shape[2] <= 1 or t.stride(2) == 1) and (t.shape[1] <= 1 or t.stride(1) == t.shape[2])
+            and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1] * t.shape[2])):
+        return t
+    return t.contiguous()
+
+
+class _MultiheadAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.mha(Qc, Kc, Vc, O), "mha")
+        ctx.A = A
+        ctx.save_for_backward(Qc, Kc, Vc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        need = ctx.needs_input_grad[1:4]
+        if not any(need):
+            return None, None, None, None
+        A, saved = ctx.A, ctx.saved_tensors
+        dO = _packed(dO.detach())
+        _on_current_stream(A, dO.device)
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(saved, need)]
+        work = None
+        if need[1] or need[2]:
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            work = torch.empty(4 * A._m * saved[0].shape[1], dtype=dO.dtype, device=dO.device)
+        _check(A.mhaBackward(saved[0], saved[1], saved[2], dO, outs[0], outs[1], outs[2], work), "mhaBackward")
+        return (None,) + tuple(outs)
+
+
+def multihead_attention(A, Q, K, V):
+    """``fused_attention`` for H heads in one call on packed operands: Q (m, H, k), K (n, H, k), V (n, H, d) -> (m, H, d); head h
+    is, bit for bit, ``fused_attention(A, Q[:, h], K[:, h], V[:, h], backward="fused")``, in the output and in every gradient.
+    Forward is ONE ``A.mha`` (one launch) into ``torch.empty``; only Q, K and V are kept.  Backward is ONE ``A.mhaBackward``
+    (two launches) on the current stream: ``torch.empty`` outputs for exactly the inputs that need a gradient, a workspace of
+    4 m H values and the transposed companion (``buildTranspose``, once per conversion: it allocates and synchronises) only
+    when K or V needs one.  Nothing of length nnz is allocated, and the handle's values and the record of them are untouched:
+    under ``torch.no_grad()`` the handle is exactly what it was.  There is no recompute route here; ``fused_attention`` keeps
+    it for one head.  Nothing runs in backward when no input needs a gradient."""
+    return _MultiheadAttention.apply(A, Q, K, V)

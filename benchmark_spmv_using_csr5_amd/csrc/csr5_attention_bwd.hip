@@ -51,9 +51,33 @@ struct AttBwdArgs {
     const uint32_t *tile_ptr;
     const VT *Q, *K, *V, *dO;
     VT *dQ, *dK, *dV; // row kernel: dQ or null; column kernel: dK, dV, one of them may be null
-    VT *work;         // [4 m]: M, r, D and one unused value per row of A; the row kernel writes (null: not wanted), the column kernel reads
+    VT *work;         // [4 m heads]: M, r, D and one unused value per (row of A, head), a row's heads adjacent; the row kernel writes
+                      // (null: not wanted), the column kernel reads
     int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
+    int heads, hper;  // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
+    int ws;           // 4 heads: the workspace values of one row
 };
+
+// the arguments of head h alone: every operand moved to that head's slice, the workspace to that head's values of row 0
+template <typename VT>
+__device__ __forceinline__ AttBwdArgs<VT> bwd_head(const AttBwdArgs<VT> &A, const int h)
+{
+    AttBwdArgs<VT> H = A;
+    const size_t ok = (size_t)h * A.k, od = (size_t)h * A.d;
+    H.Q += ok;
+    H.K += ok;
+    H.V += od;
+    H.dO += od;
+    if (H.dQ)
+        H.dQ += ok;
+    if (H.dK)
+        H.dK += ok;
+    if (H.dV)
+        H.dV += od;
+    if (H.work)
+        H.work += 4 * (size_t)h;
+    return H;
+}
 
 // s_e and dp_e of the entry (i, j)
 template <typename VT, bool VEC>
@@ -67,7 +91,8 @@ __device__ __forceinline__ void bwd_entry(const AttBwdArgs<VT> &A, const size_t 
 template <typename VT, bool VEC>
 __device__ __forceinline__ void bwd_entry_col(const AttBwdArgs<VT> &A, const size_t i, const size_t j, VT &p, VT &ds)
 {
-    const VT M = A.work[4 * i], r = A.work[4 * i + 1], D = A.work[4 * i + 2];
+    const VT *wk = A.work + (size_t)A.ws * i;
+    const VT M = wk[0], r = wk[1], D = wk[2];
     VT s, dp;
     bwd_entry<VT, VEC>(A, i, j, s, dp);
     p = exp_vt(s - M) * r;
@@ -181,7 +206,8 @@ __device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FIL
 
 // ---- lines of at most 16 entries (empty ones included): 16 lanes per line, 4 lines of the wavefront per pass ---------------
 template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_short(const AttBwdArgs<VT> &A, const long long row0, const int len, const int t0, const int rem0)
+__device__ __forceinline__ void bwd_short(const AttBwdArgs<VT> &A0, const long long row0, const int len, const int t0, const int rem0,
+                                          const int h0, const int h1)
 {
     constexpr int G = AT_G, ROWS = OMEGA / G;
     const int lane = threadIdx.x & (OMEGA - 1);
@@ -200,50 +226,53 @@ __device__ __forceinline__ void bwd_short(const AttBwdArgs<VT> &A, const long lo
         const bool rowok = (cls >> src) & 1;
         const bool act = rowok && pos < rl;
         const size_t r = (size_t)(row0 + src);
-        int other = 0;
-        if constexpr (COL) {
-            VT p = (VT)0, ds = (VT)0;
-            if (act) {
-                other = A.col[att_storage(A, rt0, rrem, pos)];
-                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, p, ds);
+        int other = 0; // the lane's column: loaded once, kept across the heads
+        if (act)
+            other = A0.col[att_storage(A0, rt0, rrem, pos)];
+        for (int h = h0; h < h1; h++) { // (uniform)
+            const AttBwdArgs<VT> A = bwd_head(A0, h);
+            if constexpr (COL) {
+                VT p = (VT)0, ds = (VT)0;
+                if (act)
+                    bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, p, ds);
+                if (A.dV)
+                    bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
+                if (A.dK)
+                    bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
+            } else {
+                VT s = neg_inf<VT>(), dp = (VT)0;
+                if (act)
+                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, s, dp);
+                const VT mx = group_max<G>(s);
+                const VT w = act ? exp_vt(s - mx) : (VT)0;
+                const VT rinv = (VT)1 / group_sum<G>(w);
+                const VT p = act ? w * rinv : (VT)0;
+                const VT pg = p * dp;
+                const VT D = group_sum<G>(act ? pg : (VT)0);
+                const VT ds = act ? p * (dp - D) : (VT)0;
+                if (A.work && rowok && pos == 0) {
+                    VT *wk = A.work + (size_t)A.ws * r;
+                    wk[0] = mx;
+                    wk[1] = rinv;
+                    wk[2] = D;
+                }
+                if (A.dQ)
+                    bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
             }
-            if (A.dV)
-                bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
-            if (A.dK)
-                bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
-        } else {
-            VT s = neg_inf<VT>(), dp = (VT)0;
-            if (act) {
-                other = A.col[att_storage(A, rt0, rrem, pos)];
-                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, s, dp);
-            }
-            const VT mx = group_max<G>(s);
-            const VT w = act ? exp_vt(s - mx) : (VT)0;
-            const VT rinv = (VT)1 / group_sum<G>(w);
-            const VT p = act ? w * rinv : (VT)0;
-            const VT pg = p * dp;
-            const VT D = group_sum<G>(act ? pg : (VT)0);
-            const VT ds = act ? p * (dp - D) : (VT)0;
-            if (A.work && rowok && pos == 0) {
-                A.work[4 * r] = mx;
-                A.work[4 * r + 1] = rinv;
-                A.work[4 * r + 2] = D;
-            }
-            if (A.dQ)
-                bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
         }
     }
 }
 
 // ---- a line of 17 .. 512 entries: one wavefront; a / b / cl: the wavefront's 512 staged values, values and indices ---------
+// One head: A holds that head's slices; first: the head that stages cl, which the later heads read back (a lane its own entries).
 template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
-                                              VT *b, int *cl)
+__device__ __forceinline__ void bwd_wave_head(const AttBwdArgs<VT> &A, const bool first, const size_t r, const int rl, const int t0,
+                                              const int rem0, VT *a, VT *b, int *cl)
 {
     const int lane = threadIdx.x & (OMEGA - 1);
     if constexpr (COL) {
         for (int j = lane; j < rl; j += OMEGA) {
-            const int i = A.col[att_storage(A, t0, rem0, j)];
+            const int i = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             VT p, ds;
             bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
             a[j] = p;
@@ -258,7 +287,7 @@ __device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const siz
     } else {
         VT mx = neg_inf<VT>();
         for (int j = lane; j < rl; j += OMEGA) {
-            const int cj = A.col[att_storage(A, t0, rem0, j)];
+            const int cj = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             VT s, dp;
             bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
             a[j] = s;
@@ -285,28 +314,39 @@ __device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const siz
         for (int j = lane; j < rl; j += OMEGA)
             a[j] = a[j] * (b[j] - D);
         if (A.work && lane == 0) {
-            A.work[4 * r] = mx;
-            A.work[4 * r + 1] = rinv;
-            A.work[4 * r + 2] = D;
+            VT *wk = A.work + (size_t)A.ws * r;
+            wk[0] = mx;
+            wk[1] = rinv;
+            wk[2] = D;
         }
         att_wave_sync();
         if (A.dQ)
             bwd_wave_acc<VT>(a, cl, rl, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
     }
-    att_wave_sync(); // (the next line's entries stay behind these reads)
+    att_wave_sync(); // (the next head's and the next line's entries stay behind these reads)
+}
+
+template <typename VT, bool VEC, bool COL>
+__device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
+                                              VT *b, int *cl, const int h0, const int h1)
+{
+    for (int h = h0; h < h1; h++) // (uniform)
+        bwd_wave_head<VT, VEC, COL>(bwd_head(A, h), h == h0, r, rl, t0, rem0, a, b, cl);
 }
 
 // ---- a line beyond 512 entries: the workgroup; a / b / cl: the AT_STAGE staged entries, red: AT_BLOCK values, red4: AT_WAVES
+// One head: A holds that head's slices; first: the head that stages cl of a line of at most AT_STAGE entries, which the later
+// heads read back (beyond AT_STAGE entries the stage holds one chunk at a time and every head walks the pattern again).
 template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
-                                             VT *b, int *cl, VT *red, VT *red4)
+__device__ __forceinline__ void bwd_hub_head(const AttBwdArgs<VT> &A, const bool first, const size_t r, const int rl, const int t0,
+                                             const int rem0, VT *a, VT *b, int *cl, VT *red, VT *red4)
 {
     const int tid = (int)threadIdx.x;
     const bool staged = rl <= AT_STAGE; // (uniform over the workgroup, as every loop bound and barrier below)
     if constexpr (COL) {
         auto fill = [&](const int base, const int n) {
             for (int jj = tid; jj < n; jj += AT_BLOCK) {
-                const int i = A.col[att_storage(A, t0, rem0, base + jj)];
+                const int i = first || !staged ? A.col[att_storage(A, t0, rem0, base + jj)] : cl[jj];
                 VT p, ds;
                 bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
                 a[jj] = p;
@@ -323,7 +363,7 @@ __device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size
     } else {
         VT mx = neg_inf<VT>();
         for (int j = tid; j < rl; j += AT_BLOCK) {
-            const int cj = A.col[att_storage(A, t0, rem0, j)];
+            const int cj = first || !staged ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             VT s, dp;
             bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
             if (staged) {
@@ -372,9 +412,10 @@ __device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size
             for (int j = tid; j < rl; j += AT_BLOCK)
                 a[j] = a[j] * (b[j] - D);
         if (A.work && tid == 0) {
-            A.work[4 * r] = mx;
-            A.work[4 * r + 1] = rinv;
-            A.work[4 * r + 2] = D;
+            VT *wk = A.work + (size_t)A.ws * r;
+            wk[0] = mx;
+            wk[1] = rinv;
+            wk[2] = D;
         }
         auto fill = [&](const int base, const int n) {
             for (int jj = tid; jj < n; jj += AT_BLOCK) {
@@ -389,11 +430,20 @@ __device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size
         if (A.dQ)
             bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.K, A.ldk, A.k, A.dQ + r * A.lddq, red);
         else
-            __syncthreads(); // (the stage is free for the next hub line)
+            __syncthreads(); // (the stage is free for the next head or hub line)
     }
 }
 
 template <typename VT, bool VEC, bool COL>
+__device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
+                                             VT *b, int *cl, VT *red, VT *red4, const int h0, const int h1)
+{
+    for (int h = h0; h < h1; h++) // (uniform)
+        bwd_hub_head<VT, VEC, COL>(bwd_head(A, h), h == h0, r, rl, t0, rem0, a, b, cl, red, red4);
+}
+
+// MH: the packed multi-head call (blockIdx.y owns a contiguous group of heads); otherwise exactly one head, known at compile time
+template <typename VT, bool VEC, bool COL, bool MH>
 __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT> A)
 {
     __shared__ VT a[AT_STAGE];
@@ -407,6 +457,11 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT>
         hub_n = 0;
     __syncthreads();
 
+    int h0 = 0, h1 = 1;
+    if constexpr (MH) {
+        h0 = (int)blockIdx.y * A.hper;
+        h1 = A.heads - h0 < A.hper ? A.heads : h0 + A.hper;
+    }
     const int wave = (int)(threadIdx.x >> 6);
     const long long row0 = (long long)blockIdx.x * AT_BLOCK + wave * OMEGA; // the wavefront's first line
     const long long r = (long long)blockIdx.x * AT_BLOCK + threadIdx.x;
@@ -418,7 +473,7 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT>
         t0 = (int)((unsigned)first / (unsigned)A.T);
         rem0 = first - t0 * A.T;
     }
-    bwd_short<VT, VEC, COL>(A, row0, len, t0, rem0);
+    bwd_short<VT, VEC, COL>(A, row0, len, t0, rem0, h0, h1);
 
     unsigned long long todo = __ballot(len > AT_G && len <= AT_WAVE_ROW);
     while (todo) {
@@ -426,7 +481,7 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT>
         todo &= todo - 1;
         bwd_wave_line<VT, VEC, COL>(A, (size_t)(row0 + src), __builtin_amdgcn_readlane(len, src), __builtin_amdgcn_readlane(t0, src),
                                     __builtin_amdgcn_readlane(rem0, src), a + wave * AT_WAVE_ROW, b + wave * AT_WAVE_ROW,
-                                    cl + wave * AT_WAVE_ROW);
+                                    cl + wave * AT_WAVE_ROW, h0, h1);
     }
 
     if (len > AT_WAVE_ROW)
@@ -438,16 +493,19 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT>
         const int ra = __builtin_amdgcn_readfirstlane(A.row_ptr[hr]);
         const int rl = __builtin_amdgcn_readfirstlane(A.row_ptr[hr + 1]) - ra;
         const int ht0 = (int)((unsigned)ra / (unsigned)A.T);
-        bwd_hub_line<VT, VEC, COL>(A, (size_t)hr, rl, ht0, ra - ht0 * A.T, a, b, cl, red, red4);
+        bwd_hub_line<VT, VEC, COL>(A, (size_t)hr, rl, ht0, ra - ht0 * A.T, a, b, cl, red, red4, h0, h1);
     }
 }
 
+// groups: the head groups over grid.y, 0 for the rule (att_heads_per_group of this side's line count)
 template <typename VT, bool COL>
-static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, AttBwdArgs<VT> A, const bool vec, hipStream_t s)
+static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, AttBwdArgs<VT> A, const int groups, const bool vec,
+                                     hipStream_t s)
 {
-    if (g.m <= 0)
+    if (g.m <= 0 || A.heads <= 0)
         return hipSuccess;
     A.lines = g.m;
+    A.hper = groups > 0 ? (A.heads + groups - 1) / groups : att_heads_per_group(g.m, A.heads);
     A.sigma = g.sigma > 0 ? g.sigma : 1;
     A.T = g.tile_elems > 0 ? g.tile_elems : OMEGA;
     A.tiles = g.p > 1 ? g.p - 1 : 0;
@@ -455,24 +513,37 @@ static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, A
     A.row_ptr = d.row_ptr;
     A.col = d.col;
     A.tile_ptr = d.tile_ptr;
-    const dim3 grid((unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK)), block(AT_BLOCK);
-    if (vec)
-        hipLaunchKernelGGL((k_attention_bwd<VT, true, COL>), grid, block, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_attention_bwd<VT, false, COL>), grid, block, 0, s, A);
+    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
+    const dim3 block(AT_BLOCK);
+    if (A.heads == 1) {
+        const dim3 grid(blocks);
+        if (vec)
+            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, false>), grid, block, 0, s, A);
+        else
+            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, false>), grid, block, 0, s, A);
+    } else {
+        const dim3 grid(blocks, (unsigned)((A.heads + A.hper - 1) / A.hper));
+        if (vec)
+            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, true>), grid, block, 0, s, A);
+        else
+            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, true>), grid, block, 0, s, A);
+    }
     return hipGetLastError();
 }
 
 // g / d: the parent's pattern (the row kernel); gt / dt: the transposed companion's (the column kernel, only when dK or dV is
 // wanted: null otherwise).  The row kernel runs when dQ is wanted or the column kernel needs the workspace.
 template <typename VT>
-static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
-                                      int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
-                                      void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads,
+                                      int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
+                                      const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work,
+                                      hipStream_t s)
 {
     AttBwdArgs<VT> A{};
     A.k = k;
     A.d = dcols;
+    A.heads = heads;
+    A.ws = 4 * heads;
     A.Q = (const VT *)Q;
     A.K = (const VT *)K;
     A.V = (const VT *)V;
@@ -484,9 +555,9 @@ static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, 
     A.lddq = lddq;
     A.lddk = lddk;
     A.lddv = lddv;
-    // 16-byte loads: every row of Q, K, V and dO starts on a 16-byte boundary (a chain shorter than one block of 32 bytes takes
-    // element loads anyway)
-    bool vec = true;
+    // 16-byte loads: every head's slice of every row of Q, K, V and dO starts on a 16-byte boundary (a chain shorter than one
+    // block of 32 bytes takes element loads anyway)
+    bool vec = heads == 1 || (((size_t)k * sizeof(VT)) % 16 == 0 && ((size_t)dcols * sizeof(VT)) % 16 == 0);
     const void *ptrs[4] = {Q, K, V, dO};
     const int lds[4] = {ldq, ldk, ldv, lddo};
     for (int i = 0; i < 4; i++)
@@ -498,7 +569,7 @@ static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, 
         R.dQ = k > 0 ? (VT *)dQ : nullptr;
         R.work = column ? (VT *)work : nullptr;
         if (R.dQ || R.work)
-            e = attention_bwd_side<VT, false>(g, d, R, vec, s);
+            e = attention_bwd_side<VT, false>(g, d, R, groups, vec, s);
     }
     if (e == hipSuccess && column) {
         AttBwdArgs<VT> C = A;
@@ -506,41 +577,52 @@ static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, 
         C.dV = dcols > 0 ? (VT *)dV : nullptr;
         C.work = (VT *)work;
         if (C.dK || C.dV)
-            e = attention_bwd_side<VT, true>(*gt, *dt, C, vec, s);
+            e = attention_bwd_side<VT, true>(*gt, *dt, C, groups, vec, s);
     }
     return e;
 }
 
 // The product build compiles this file once per value type (-DCSR5_ATTENTION_BWD_ONLY_F64 / _F32), as csr5_attention.hip.
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
-hipError_t launch_attention_bwd_f64(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
-                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
-                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+hipError_t launch_mha_bwd_f64(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
+                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
+                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
 {
-    return attention_bwd_typed<double>(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+    return attention_bwd_typed<double>(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV,
+                                       lddv, work, s);
 }
 #endif
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F64)
-hipError_t launch_attention_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
-                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
-                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+hipError_t launch_mha_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
+                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
+                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
 {
-    return attention_bwd_typed<float>(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+    return attention_bwd_typed<float>(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV,
+                                      lddv, work, s);
 }
 #endif
 
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
-hipError_t launch_attention_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const void *Q,
-                                    int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo,
-                                    void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
+hipError_t launch_mha_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
+                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
+                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
+
+hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type, int heads,
+                          int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
+                          const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+{
+    return value_type == CSR5HIP_F64 ? launch_mha_bwd_f64(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq,
+                                                          dK, lddk, dV, lddv, work, s)
+                                     : launch_mha_bwd_f32(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq,
+                                                          dK, lddk, dV, lddv, work, s);
+}
 
 hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
                                 const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
                                 int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
 {
-    return value_type == CSR5HIP_F64
-               ? launch_attention_bwd_f64(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s)
-               : launch_attention_bwd_f32(g, d, gt, dt, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work, s);
+    return launch_mha_bwd(g, d, gt, dt, value_type, 1, 0, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work,
+                          s);
 }
 #endif
 

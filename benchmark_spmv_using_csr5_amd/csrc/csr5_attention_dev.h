@@ -15,6 +15,21 @@ constexpr int AT_WAVE_ROW = 512;                   // entries a wavefront stages
 constexpr int AT_STAGE = AT_WAVES * AT_WAVE_ROW;   // entries the workgroup stages: a hub row's chunk
 constexpr int AT_HUB_BLOCKS = 4;                   // column blocks of 64 whose accumulators a lane of a hub row holds
 
+// Heads of one workgroup of a packed multi-head launch; grid.y = ceil(heads / this) contiguous head groups.  A function of the
+// pattern's line count and of heads, of nothing else: enough groups to bring the grid to AT_GRID_TARGET workgroups (256 compute
+// units, 4 workgroups each), but at most ceil(heads / 2) groups, so that the pattern work is shared wherever two heads are left
+// to share it (an odd head count leaves the last group of a two-head split with one head).  No bit depends on it.
+constexpr long long AT_GRID_TARGET = 1024;
+inline int att_heads_per_group(const long long lines, const int heads)
+{
+    const long long blocks = lines > 0 ? (lines + AT_BLOCK - 1) / AT_BLOCK : 1;
+    long long groups = (AT_GRID_TARGET + blocks - 1) / blocks;
+    const long long cap = ((long long)heads + 1) / 2;
+    groups = groups < cap ? groups : cap;
+    groups = groups < 1 ? 1 : groups;
+    return (int)((heads + groups - 1) / groups);
+}
+
 // storage position of the entry of rank j inside a row whose first entry has CSR rank t0 * T + rem0.  ARGS carries the pattern:
 // T (tile_elems), sigma, tiles (p - 1), recip (sigma's reciprocal in 20 fractional bits, rounded up) and tile_ptr.
 template <typename ARGS>

@@ -251,12 +251,20 @@ hipError_t launch_row_softmax_grad(int m, const int32_t *row_ptr, int value_type
 // the tile-ordered column_index (g, d: CSR5 form) and writes EVERY row of O in columns 0 .. dcols-1; no workspace
 hipError_t launch_attention(const Geometry &g, const DeviceArrays &d, int value_type, const void *Q, int ldq, const void *K, int ldk,
                             int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
+// the same for `heads` heads on packed operands (head h in columns h k .. / h dcols ..) in one launch; groups: the head groups over
+// grid.y, 0 for the rule, a function of (m, heads).  heads = 1 is launch_attention
+hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, const void *Q, int ldq,
+                      const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
 // csr5_attention_bwd.hip: the gradients of launch_attention's O for Q, K and V.  The row kernel walks the parent's pattern (g, d) and
 // writes dQ and the workspace (4 values per row); the column kernel walks the transposed companion's (gt, dt; null when neither dK
 // nor dV is wanted) and writes dK and dV.  A null output is not wanted; EVERY row of a wanted one is written in its k / dcols columns
 hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
                                 const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
                                 int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
+// the same for `heads` heads on packed operands; the workspace holds 4 values per (row, head), a row's heads adjacent
+hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type, int heads,
+                          int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
+                          const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

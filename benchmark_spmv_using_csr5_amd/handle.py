@@ -322,6 +322,100 @@ class anonymouslibHandle:
                                                     _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv),
                                                     _ptr(work))
 
+    # -- attention for all heads in one launch (csr5hip.h csr5hip_mha / csr5hip_mha_backward) -------
+    def _mha_args(self, who: str, ins, outs, work):
+        """the checks of ``attention``'s operands for packed 3-D tensors (rows, heads, width): ValueError, naming the operand,
+        unless each has the handle's dtype, its row count, stride(2) == 1, stride(1) == width and rows that do not overlap; the
+        head counts and widths agree; no output shares storage with an input, another output or ``work``; all live on one GPU.
+        Returns (heads, k, d)."""
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        for name, t, rows, width in ins + outs:
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"{who}: {name} must be a torch tensor")
+            if str(t.dtype) != dt:
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 3 or t.shape[0] != rows:
+                raise ValueError(f"{who}: {name} must have shape ({rows}, heads, {width}), not {tuple(t.shape)}")
+            if t.numel() and t.shape[2] > 1 and t.stride(2) != 1:
+                raise ValueError(f"{who}: {name} must have stride(2) == 1, not {t.stride()}")
+            if t.numel() and t.shape[1] > 1 and t.stride(1) != t.shape[2]:
+                raise ValueError(f"{who}: {name} must be packed with stride(1) == {width} = {t.shape[2]}, not {t.stride()}")
+            if t.numel() and t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2]:
+                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads * {width} = {t.shape[1] * t.shape[2]})")
+        Q, V = ins[0][1], ins[2][1]
+        heads, k, d = int(Q.shape[1]), int(Q.shape[2]), int(V.shape[2])
+        for name, t, _, width in ins[1:] + outs:
+            if t.shape[1] != heads:
+                raise ValueError(f"{who}: Q has {heads} heads, {name} {t.shape[1]}")
+            want = k if width == "k" else d
+            if t.shape[2] != want:
+                first = "Q" if width == "k" else "V"
+                raise ValueError(f"{who}: {first} has width {want}, {name} {t.shape[2]}")
+        if work is not None or any(name in ("dK", "dV") for name, _, _, _ in outs):
+            if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
+                raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
+            if str(work.dtype) != dt:
+                raise ValueError(f"{who}: work has dtype {work.dtype}, the handle holds {dt}")
+            if work.dim() != 1 or work.shape[0] < 4 * self._m * heads:
+                raise ValueError(f"{who}: work must have shape ({4 * self._m * heads},) or longer, not {tuple(work.shape)}")
+            if not work.is_contiguous():
+                raise ValueError(f"{who}: work must be contiguous, not stride {work.stride()}")
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        scratch = (("work", work, 0, ""),) if work is not None else ()
+        for i, (oname, o, _, _) in enumerate(outs):
+            for name, t, _, _ in ins + outs[:i] + scratch:
+                if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                    raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
+        for name, t, _, _ in ins + outs + scratch:
+            if t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        if any(t.device != Q.device for _, t, _, _ in ins + outs + scratch):
+            raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t, _, _ in ins + outs + scratch))
+        return heads, k, d
+
+    @staticmethod
+    def _mha_ld(t) -> int:
+        w = int(t.shape[1]) * int(t.shape[2])
+        return max(int(t.stride(0)), w) if t.shape[0] > 1 and w else w
+
+    def mha(self, Q, K, V, O) -> int:
+        """``attention`` for all heads in ONE launch: Q (m, H, k), K (n, H, k), V (n, H, d) and O (m, H, d), packed (stride(2) == 1,
+        stride(1) == width; stride(0) >= H * width, so a slice of a wider tensor is legal).  Head h of O has, bit for bit, what
+        ``attention(Q[:, h], K[:, h], V[:, h], O[:, h])`` writes; EVERY row of O is written in all H * d columns, so O may be
+        ``torch.empty``; O shares storage with none of the inputs.  The handle is left untouched.  Anything else raises
+        ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        heads, k, d = self._mha_args("mha", ins, (("O", O, self._m, "d"),), None)
+        ld = self._mha_ld
+        return self.mha_ptr(heads, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def mha_ptr(self, heads: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
+        """csr5hip_mha on raw device pointers (or tensors): packed Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
+        return self._lib.csr5hip_mha(self._h, int(heads), _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                     _ptr(O), int(ldo))
+
+    def mhaBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
+        """``attentionBackward`` for all heads in TWO launches on ``mha``'s packed operands: dO (m, H, d) in; dQ (m, H, k),
+        dK (n, H, k), dV (n, H, d) out, each written in every row and head (so they may be ``torch.empty``) or None when not
+        wanted; head h has the bits of ``attentionBackward`` on that head's slices.  dK and dV need ``work``, a contiguous 1-D
+        tensor of at least 4 m H values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
+        An output shares storage with no input, no other output and not with ``work``.  Anything else raises ValueError before
+        the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        heads, k, d = self._mha_args("mhaBackward", ins, outs, work)
+        ld = self._mha_ld
+        return self.mha_backward_ptr(heads, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ, ld(dQ) if dQ is not None else heads * k,
+                                     dK, ld(dK) if dK is not None else heads * k, dV, ld(dV) if dV is not None else heads * d, work)
+
+    def mha_backward_ptr(self, heads: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK,
+                         lddk: int, dV, lddv: int, work) -> int:
+        """csr5hip_mha_backward on raw device pointers (or tensors); None for an output that is not wanted"""
+        return self._lib.csr5hip_mha_backward(self._h, int(heads), _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv),
+                                              int(d), _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV),
+                                              int(lddv), _ptr(work))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

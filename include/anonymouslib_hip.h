@@ -175,6 +175,23 @@ public:
                                                (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk, (void *)dV, lddv, (void *)work)
                   : _err;
     }
+    // extension: attention for `heads` heads in one launch on packed operands: head h in columns h k .. h k + k of Q and K (ldq, ldk >=
+    // heads k) and h d .. h d + d of V and O (ldv, ldo >= heads d); head h has the bits of attention on those slices (csr5hip_mha)
+    int mha(int heads, const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv,
+            int d, ANONYMOUSLIB_VT *O, int ldo)
+    {
+        return _h ? csr5hip_mha(_h, heads, (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d, (void *)O, ldo) : _err;
+    }
+    // extension: attentionBackward for `heads` heads in two launches on the packed layout (dO, dV as V; dQ, dK as Q); work: 4 m heads
+    // values of scratch, needed (as the transposed companion) only for dK or dV (csr5hip_mha_backward)
+    int mhaBackward(int heads, const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V,
+                    int ldv, int d, const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk,
+                    ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work)
+    {
+        return _h ? csr5hip_mha_backward(_h, heads, (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d,
+                                         (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk, (void *)dV, lddv, (void *)work)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

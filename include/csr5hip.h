@@ -407,6 +407,46 @@ int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_
 int csr5hip_attention_backward(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k,
                                const void *d_V, int ldv, int d, const void *d_dO, int lddo,
                                void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work);
+/* Extension (not in the reference): csr5hip_attention for `heads` heads in ONE launch, on PACKED operands: head h (0 <= h < heads)
+ * reads Q[:, h k .. h k + k) and K[:, h k .. h k + k), reads V[:, h d .. h d + d) and writes O[:, h d .. h d + d).  Rows are
+ * row-major with ldq, ldk >= heads * k and ldv, ldo >= heads * d (the layout (rows, heads, width) of every framework); the operands
+ * may themselves be column slices of wider tensors.
+ * DEFINITION BY REFERENCE: head h of O is, bit for bit, what
+ *     csr5hip_attention(h, Q + h k, ldq, K + h k, ldk, k, V + h d, ldv, d, O + h d, ldo)
+ * writes -- for every row class, for non-finite scores, for rows without entries (+0) and for k = 0 -- so the summation orders, the
+ * score chain, the one reciprocal per row and the determinism contract are that call's.  One rule differs: 16-byte loads are taken
+ * only where every head's slice of every row is 16-byte aligned, i.e. under that call's conditions and (k * sizeof) % 16 == 0;
+ * either load width feeds the same chains.  heads = 1 IS csr5hip_attention.
+ * What is done once for all heads: a row's bounds and class, an entry's rank -> storage map and its column load; per entry the
+ * heads are taken one after the other.  The heads may be split into contiguous groups over the grid's second dimension; the
+ * number of groups is a function of (m, heads) alone and no bit depends on it.
+ * As csr5hip_attention: nothing is allocated or read back, the call only enqueues one kernel on the handle's stream from the first
+ * call on (capturable), and the handle's values, x, options, csr5hip_info and device_bytes are neither read nor changed.  EVERY row
+ * of O is written in all heads * d columns; columns heads * d .. ldo-1 are never written.
+ * Returns, decided on the host in this order: CSR5HIP_INVALID_ARGUMENT for a null handle, heads < 0, k < 0, d < 0, ldq or ldk
+ * < heads * k, ldv or ldo < heads * d (compared in 64 bits), and with heads > 0 for the null operands csr5hip_attention rejects;
+ * CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format; CSR5HIP_UNKOWN_FORMAT before inputCSR.  heads = 0, like d = 0 or m = 0, is then a
+ * successful no-op.  Single handles only. */
+int csr5hip_mha(csr5hip_handle h, int heads,
+                const void *d_Q, int ldq, const void *d_K, int ldk, int k,
+                const void *d_V, int ldv, int d, void *d_O, int ldo);
+/* Extension (not in the reference): csr5hip_attention_backward for `heads` heads in TWO launches, on csr5hip_mha's packed layout:
+ * dO and dV as V (head h in columns h d .. h d + d), dQ and dK as Q (columns h k .. h k + k); lddo, lddv >= heads * d and lddq,
+ * lddk >= heads * k.  Head h of every wanted output is, bit for bit, what csr5hip_attention_backward on the same slices writes;
+ * 16-byte loads only where additionally (k * sizeof) % 16 == 0 and (d * sizeof) % 16 == 0.  Any output may be null; every row of a
+ * wanted one is written in all its heads * k (heads * d) columns and nothing beyond.
+ * d_work: caller-owned scratch of 4 * m * heads values of the handle's type (layout private; the heads of a row are adjacent),
+ * needed only when dK or dV is wanted.  dK or dV REQUIRES THE TRANSPOSED COMPANION (csr5hip_build_transpose; never built lazily).
+ * The head groups of the row kernel are a function of (m, heads), those of the column kernel of (n, heads).
+ * Allocates nothing, reads nothing back, only enqueues (capturable), leaves the handle untouched.
+ * Returns, in this order: CSR5HIP_INVALID_ARGUMENT for a null handle, heads < 0, k < 0, d < 0 or a leading dimension below heads
+ * times its width (64-bit comparison); CSR5HIP_INVALID_ARGUMENT, with heads > 0, for the null operands csr5hip_attention_backward
+ * rejects; CSR5HIP_INVALID_ARGUMENT with a csr5hip_last_error text when dK or dV is wanted and there is no companion;
+ * CSR5HIP_UNSUPPORTED_CSR_SPMV in CSR format; CSR5HIP_UNKOWN_FORMAT before inputCSR.  heads = 0 is then a successful no-op. */
+int csr5hip_mha_backward(csr5hip_handle h, int heads,
+                const void *d_Q, int ldq, const void *d_K, int ldk, int k,
+                const void *d_V, int ldv, int d, const void *d_dO, int lddo,
+                void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work);
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);

@@ -73,11 +73,12 @@ template <typename K, typename... Args>
 inline void emu_launch(K kernel, dim3 grid, dim3 block, Args... args)
 {
     if (block.x != 256) { fprintf(stderr, "emu: block %u\n", block.x); abort(); }
-    for (unsigned b = 0; b < grid.x; b++) {
-        std::vector<std::thread> ts;
-        for (unsigned t = 0; t < 256; t++)
-            ts.emplace_back([=] { threadIdx = {t, 0, 0}; blockIdx = {b, 0, 0}; kernel(args...); });
-        for (auto &t : ts) t.join();
-    }
+    for (unsigned by = 0; by < grid.y; by++)
+        for (unsigned b = 0; b < grid.x; b++) {
+            std::vector<std::thread> ts;
+            for (unsigned t = 0; t < 256; t++)
+                ts.emplace_back([=] { threadIdx = {t, 0, 0}; blockIdx = {b, by, 0}; kernel(args...); });
+            for (auto &t : ts) t.join();
+        }
 }
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) emu_launch(kernel, grid, block, __VA_ARGS__)
