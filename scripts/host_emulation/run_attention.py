@@ -5,6 +5,9 @@ a stand-alone program on matrices of tests/zoo.py converted by the oracle.
 
     python scripts/host_emulation/run_attention.py [--matrices kat0,duplicates,aligned64,aligned1024,one-row] [--cxx clang++]
 
+--matrices also takes class-edges and dealt of tests/attention_edges.py (a line on every class edge, hubs in every workgroup) and
+NAME^T for the transpose of any of them.
+
 Per matrix, precision and (k, d): O against a float64 numpy reference (1e3 unit roundoffs of the largest |V| sum: a check of the
 indexing, not the accuracy test), rows without entries exactly +0, nothing written beyond column d, and equal bits for sigma = 4,
 sigma = 7 with padded leading dimensions (element loads) and sigma = 16 (16-byte loads).  This exercises the indexing, the row
@@ -23,8 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle.csr5_oracle import Oracle  # noqa: E402
-from tests import sddmm_reference as S  # noqa: E402
-from tests import zoo  # noqa: E402
+from scripts.host_emulation.run_attention_backward import matrices  # noqa: E402
 
 KD = ((1, 1), (3, 5), (8, 16), (40, 70), (0, 7), (5, 300))
 
@@ -81,13 +83,12 @@ def main():
     ap.add_argument("--cxx", default="/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else "clang++")
     args = ap.parse_args()
     orc = Oracle()
-    mats = {m.name: m for m in zoo.small_zoo()}
-    mats["duplicates"] = S.duplicates_matrix()
+    mats = matrices()
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "attention_host")
         build(args.cxx, exe)
         for name in args.matrices.split(","):
-            mat = mats[name]
+            mat = mats(name)
             for dtype in (np.float64, np.float32):
                 u = float(np.finfo(dtype).eps) / 2
                 for k, d in KD:

@@ -5,6 +5,9 @@ and their transposes, both converted by the oracle (the transpose plays the tran
 
     python scripts/host_emulation/run_attention_backward.py [--matrices kat0,duplicates,...] [--kd 3x5,8x16] [--cxx clang++]
 
+--matrices also takes class-edges and dealt of tests/attention_edges.py (a line on every class edge, hubs in every workgroup) and
+NAME^T for the transpose of any matrix.
+
 Per matrix, precision and (k, d): dQ, dK and dV against a float64 numpy reference (1e3 unit roundoffs of the gradient expression on
 absolute values: a check of the indexing, not the accuracy test), rows and columns without entries exactly +0, nothing written
 beyond column k or d, dQ alone without a workspace, and equal bits for sigma = 4, sigma = 7 with padded leading dimensions
@@ -25,6 +28,7 @@ if ROOT not in sys.path:
 
 from benchmark_spmv_using_csr5_amd import matrices as M  # noqa: E402
 from oracle.csr5_oracle import Oracle  # noqa: E402
+from tests import attention_edges as E  # noqa: E402
 from tests import sddmm_reference as S  # noqa: E402
 from tests import zoo  # noqa: E402
 
@@ -40,6 +44,15 @@ def transpose(mat):
     rp = np.zeros(mat.n + 1, dtype=np.int32)
     rp[1:] = np.cumsum(np.bincount(cols, minlength=mat.n))
     return M.CsrMatrix(mat.n, mat.m, rp, rows[order].astype(np.int32), np.ones(mat.nnz), mat.name + "^T")
+
+
+def matrices():
+    """name -> matrix: tests/zoo.py's, the duplicates matrix, class-edges and dealt; NAME^T is the transpose"""
+    mats = {m.name: m for m in zoo.small_zoo()}
+    mats["duplicates"] = S.duplicates_matrix()
+    mats["class-edges"] = E.class_edges()
+    mats["dealt"] = E.dealt()
+    return lambda name: transpose(mats[name[:-2]]) if name.endswith("^T") else mats[name]
 
 
 def build(cxx, out):
@@ -118,13 +131,12 @@ def main():
     args = ap.parse_args()
     kds = [tuple(int(v) for v in kd.split("x")) for kd in args.kd.split(",")]
     orc = Oracle()
-    mats = {m.name: m for m in zoo.small_zoo()}
-    mats["duplicates"] = S.duplicates_matrix()
+    mats = matrices()
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "attention_bwd_host")
         build(args.cxx, exe)
         for name in args.matrices.split(","):
-            mat = transpose(mats[name[:-2]]) if name.endswith("^T") else mats[name]
+            mat = mats(name)
             matT = transpose(mat)
             empty = (np.diff(mat.row_ptr) == 0, np.diff(matT.row_ptr) == 0, np.diff(matT.row_ptr) == 0)
             for dtype in (np.float64, np.float32):

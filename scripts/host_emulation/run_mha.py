@@ -7,6 +7,9 @@ the transpose, converted at another sigma, plays the transposed companion.
     python scripts/host_emulation/run_mha.py [--matrices kat0,duplicates,aligned64,aligned1024,one-row] [--dtypes f64,f32]
                                              [--heads 1,3] [--kd 3x5,8x16,5x300] [--cxx clang++]
 
+--matrices also takes class-edges and dealt of tests/attention_edges.py (a line on every class edge, hubs in every workgroup) and
+NAME^T for the transpose of any matrix.
+
 Per matrix, precision, heads in {1, 3} and (k, d) in {(3, 5), (8, 16), (5, 300)}, forward and backward:
   * head h of the packed call has the same bits as the SINGLE-HEAD launcher on that head's slices of the same arrays;
   * nothing is written beyond column heads * d (heads * k) of an output, and nothing at all into an output that is not wanted;
@@ -29,9 +32,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle.csr5_oracle import Oracle  # noqa: E402
-from scripts.host_emulation.run_attention_backward import transpose  # noqa: E402
-from tests import sddmm_reference as S  # noqa: E402
-from tests import zoo  # noqa: E402
+from scripts.host_emulation.run_attention_backward import matrices, transpose  # noqa: E402
 
 HEADS = (1, 3)
 KD = ((3, 5), (8, 16), (5, 300))
@@ -119,14 +120,13 @@ def main():
     heads = [int(h) for h in args.heads.split(",")]
     kds = [tuple(int(v) for v in kd.split("x")) for kd in args.kd.split(",")]
     orc = Oracle()
-    mats = {m.name: m for m in zoo.small_zoo()}
-    mats["duplicates"] = S.duplicates_matrix()
+    mats = matrices()
     with tempfile.TemporaryDirectory() as tmp:
         fwd, bwd = os.path.join(tmp, "mha_host"), os.path.join(tmp, "mha_bwd_host")
         build(args.cxx, "mha_main.cpp", fwd)
         build(args.cxx, "mha_bwd_main.cpp", bwd)
         for name in args.matrices.split(","):
-            mat = mats[name]
+            mat = mats(name)
             matT = transpose(mat)
             conv = {s: orc.convert(64, s, mat.m, mat.row_ptr, mat.col, np.ones(mat.nnz)) for s in (4, 7, 16)}
             convT = {s: orc.convert(64, s, matT.m, matT.row_ptr, matT.col, np.ones(matT.nnz)) for s in (4, 7, 16)}

@@ -7,7 +7,9 @@ Line classes of the two kernels and where they are met.  The row kernel (dQ, the
 half-empty, ...), 17 .. 512 (aligned64, row 5 of the duplicates matrix), 513 .. 2 048 (aligned1024) and beyond (hub, two-hubs,
 one-row).  The column kernel (dK, dV) decides by the COLUMN's length, and the zoo's columns are short: only the transposes of
 aligned64 (columns of 64 entries), aligned1024 (1 024), two-hubs (5 000 and 7 000) and hub (9 000) reach its wavefront and
-workgroup classes.  Widths 70 and 40 have a second column block; 300 has a second group of four blocks in every output.
+workgroup classes.  Widths 70 and 40 have a second column block; 300 has a second group of four blocks in every output.  None of these
+lines sits ON a class edge and every line beyond 512 entries lies in workgroup 0: the edges, hubs in later workgroups, second
+column blocks of width 1 and dQ, dK and dV bit for bit are in tests/test_gpu_attention_edges.py.
 
 THE BOUND of the accuracy test.  tests/test_gpu_attention_autograd.py derives, for the unfused chain, |grad - ref| <= STAGES rho A
 with A the gradient expression on absolute values and rho the largest relative error of a factor.  The fused backward is, per

@@ -5,7 +5,9 @@ handle, special values, graph capture, and the autograd wrapper (gradcheck, grad
 
 Row classes of the kernel and where they are met: at most 16 entries (kat0, half-empty, ...), 17 .. 512 (aligned64, row 5 of the
 duplicates matrix), 513 .. 2 048 (aligned1024) and beyond (hub, two-hubs, one-row); d = 70 has a second column block of 6
-columns, d = 300 (the wide test) a second group of four blocks."""
+columns, d = 300 (the wide test) a second group of four blocks.  None of these rows sits ON a class edge and every row beyond 512
+entries lies in workgroup 0: the edges (17, 63 | 64 | 65, 511 | 512 | 513, 2 048 | 2 049, 4 096 | 4 097), hubs in later
+workgroups, second column blocks of width 1 and the output bit for bit are in tests/test_gpu_attention_edges.py."""
 import functools
 
 import numpy as np

@@ -6,7 +6,10 @@ on the single-head kernel alone.
 
 Shapes (heads, k, d) and why: (1, 8, 16) the single-head instantiation; (2, 8, 16) every slice 16-byte aligned: 16-byte loads;
 (3, 3, 5) element loads; (3, 10, 6) in fp32 and (3, 5, 6) in fp64: head 0 is 16-byte aligned and head 1 is not; (5, 1, 1);
-(2, 13, 70) a second column block per head.  With three heads the head groups hold two heads and one."""
+(2, 13, 70) a second column block per head.  With three heads the head groups hold two heads and one; no (lines, heads) of this
+file gives a group more than two heads.  Groups of three heads and of all heads, the staged columns reused by the later heads at
+exactly 512 and 2 048 entries, hubs in later workgroups and ``mhaBackward`` against the float64 reference are in
+tests/test_gpu_attention_edges.py."""
 import functools
 
 import numpy as np
