@@ -184,6 +184,19 @@ SYMBOLS = [
     ("csr5hip_load", C.c_int, [C.c_char_p, C.POINTER(_H), C.POINTER(DeviceCsrStruct)]),
 ]
 
+# the biased attention calls, bound by load() like SYMBOLS: heads, scale (double), slopes, then csr5hip_mha's / csr5hip_mha_backward's
+# arguments, the backward's followed by dS and ldds.  A list of their own, as their declarations are in a header of their own
+# (include/csr5hip_bias.h, included by csr5hip.h): tests/test_mha_host.py pins SYMBOLS' entries that begin with "csr5hip_mha" to the
+# two plain calls, and tests/test_host.py pins SYMBOLS to the names declared in the text of csr5hip.h.  That test's
+# header-against-exports comparison therefore does not see these two; tests/test_mha_bias_host.py makes it for them.
+SYMBOLS_BIASED = [
+    ("csr5hip_mha_biased", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("csr5hip_mha_biased_backward", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+]
+
 _lib = None
 
 
@@ -206,7 +219,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -34,7 +34,9 @@ backward recomputes through ``attention`` and therefore DOES leave the handle as
 ``backward="fused"`` is one ``A.attentionBackward`` call instead, which leaves the handle untouched as the forward does.
 
 ``multihead_attention(A, Q, K, V)`` is ``fused_attention(..., backward="fused")`` for H heads at once on packed operands
-(rows, H, width): one ``A.mha`` forward, one ``A.mhaBackward`` backward, the handle untouched by both.
+(rows, H, width): one ``A.mha`` forward, one ``A.mhaBackward`` backward, the handle untouched by both.  With ``scale``, ``bias``
+or ``slopes`` it computes ``softmax(scale Q K^T + slopes[h] bias)`` through ``A.mhaBiased`` / ``A.mhaBiasedBackward``: the bias is
+nnz values in CSR order and is given to the handle as ``spmm``'s ``val`` is, so the handle then holds it.
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -297,7 +299,60 @@ class _MultiheadAttention(torch.autograd.Function):
         return (None,) + tuple(outs)
 
 
-def multihead_attention(A, Q, K, V):
+class _BiasedMultiheadAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias, slopes):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        _on_current_stream(A, Qc.device)
+        val = key = None
+        if bias is not None:
+            val = bias.detach()
+            if not val.is_contiguous():
+                val = val.contiguous()
+            key = _key(val)
+            _give_values(A, val, key)  # (the handle now holds the bias: see the module docstring)
+        else:
+            key = getattr(A, "_autograd_key", None)  # (bias=None: the record of the values the handle holds now, checked in backward)
+        sl = slopes.detach().contiguous() if slopes is not None else None
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.mhaBiased(Qc, Kc, Vc, O, scale=scale, slopes=sl), "mhaBiased")
+        ctx.A, ctx.scale, ctx.key = A, scale, key
+        ctx.save_for_backward(Qc, Kc, Vc, val, sl)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        need = ctx.needs_input_grad[1:4]
+        Q, K, V, val, sl = ctx.saved_tensors
+        need_bias = val is not None and ctx.needs_input_grad[5]
+        need_slopes = sl is not None and ctx.needs_input_grad[6]
+        if not (any(need) or need_bias or need_slopes):
+            return (None,) * 7
+        A = ctx.A
+        dO = _packed(dO.detach())
+        _on_current_stream(A, dO.device)
+        if val is not None:
+            _give_values(A, val, ctx.key)  # (another forward may have given the handle other values: both kernels read the forward's)
+        elif getattr(A, "_autograd_key", None) != ctx.key:
+            raise RuntimeError("multihead_attention: the handle's values were replaced between this forward (bias=None: whatever the "
+                               "handle held) and its backward; give the bias as a tensor, which backward hands to the handle again")
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
+        work = None
+        if need[1] or need[2]:
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        dS = torch.empty((A._nnz, Q.shape[1]), dtype=dO.dtype, device=dO.device) if need_bias or need_slopes else None
+        _check(A.mhaBiasedBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, scale=ctx.scale, slopes=sl, dS=dS), "mhaBiasedBackward")
+        grad_bias = grad_slopes = None
+        if need_bias:
+            grad_bias = (dS * sl).sum(1) if sl is not None else dS.sum(1)
+        if need_slopes:
+            grad_slopes = (dS * val[:, None]).sum(0)
+        return (None,) + tuple(outs) + (None, grad_bias, grad_slopes)
+
+
+def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     """``fused_attention`` for H heads in one call on packed operands: Q (m, H, k), K (n, H, k), V (n, H, d) -> (m, H, d); head h
     is, bit for bit, ``fused_attention(A, Q[:, h], K[:, h], V[:, h], backward="fused")``, in the output and in every gradient.
     Forward is ONE ``A.mha`` (one launch) into ``torch.empty``; only Q, K and V are kept.  Backward is ONE ``A.mhaBackward``
@@ -305,5 +360,30 @@ def multihead_attention(A, Q, K, V):
     4 m H values and the transposed companion (``buildTranspose``, once per conversion: it allocates and synchronises) only
     when K or V needs one.  Nothing of length nnz is allocated, and the handle's values and the record of them are untouched:
     under ``torch.no_grad()`` the handle is exactly what it was.  There is no recompute route here; ``fused_attention`` keeps
-    it for one head.  Nothing runs in backward when no input needs a gradient."""
-    return _MultiheadAttention.apply(A, Q, K, V)
+    it for one head.  Nothing runs in backward when no input needs a gradient.
+
+    With any of ``scale``, ``bias`` and ``slopes`` given (all three ``None`` is the code path above, unchanged) the weights are
+    ``softmax(scale * Q K^T + slopes[h] * bias)`` over the stored entries, by ONE ``A.mhaBiased`` forward and ONE
+    ``A.mhaBiasedBackward`` backward:
+
+    * ``scale``   a Python float, ``None`` for 1.0; not differentiable.
+    * ``bias``    nnz values in CSR order (edge features, a distance bias, a mask of 0 / -Inf), handed to the handle as
+                  ``spmm``'s ``val`` is: ``A.updateValues`` unless the handle already holds exactly this tensor, so AFTER THE
+                  CALL THE HANDLE HOLDS THE BIAS, and ``updateValues``'s aliasing rule applies.  Differentiable.  ``None``: whatever
+                  values the handle holds are the bias, and nothing flows back to them.  THEY MUST STILL BE THERE IN BACKWARD:
+                  nothing is kept to give again.  Where another call of this module has replaced them in between, backward
+                  raises RuntimeError (the record of the handle's values differs); a direct ``A.updateValues`` between forward
+                  and backward of values that this module never gave is NOT seen, and backward then differentiates the
+                  function of the new values.
+    * ``slopes``  H values, one per head (ALiBi), ``None`` for none; differentiable, which needs ``bias`` as a tensor (the
+                  gradient is formed from it) -- ValueError otherwise.
+
+    Backward gives the handle the forward's bias again when another forward has replaced it in between.  Only when ``bias`` or
+    ``slopes`` needs a gradient an (nnz, H) tensor of score gradients dS is allocated and written; ``grad_bias`` is
+    ``(dS * slopes).sum(1)`` and ``grad_slopes`` ``(dS * bias[:, None]).sum(0)``, in torch.  Single-head users pass H = 1 on a
+    ``(rows, 1, width)`` view."""
+    if scale is None and bias is None and slopes is None:
+        return _MultiheadAttention.apply(A, Q, K, V)
+    if slopes is not None and bias is None and slopes.requires_grad and torch.is_grad_enabled():
+        raise ValueError("multihead_attention: slopes needs a gradient, which is formed from the bias: give bias as a tensor")
+    return _BiasedMultiheadAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias, slopes)

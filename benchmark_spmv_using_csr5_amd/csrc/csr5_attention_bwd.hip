@@ -37,499 +37,11 @@
 // every FMA is written out (fma_vt); nothing else may be contracted
 #pragma clang fp contract(off)
 
-#include "csr5_attention_dev.h"
+// the kernel templates (csr5_attention_bwd_kern.h, shared with the biased entry point's translation unit
+// csr5_attention_bwd_bias.hip)
+#include "csr5_attention_bwd_kern.h"
 
 namespace csr5 {
-
-template <typename VT>
-struct AttBwdArgs {
-    int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
-    int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
-    unsigned recip;
-    const int32_t *row_ptr;
-    const int32_t *col;
-    const uint32_t *tile_ptr;
-    const VT *Q, *K, *V, *dO;
-    VT *dQ, *dK, *dV; // row kernel: dQ or null; column kernel: dK, dV, one of them may be null
-    VT *work;         // [4 m heads]: M, r, D and one unused value per (row of A, head), a row's heads adjacent; the row kernel writes
-                      // (null: not wanted), the column kernel reads
-    int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
-    int heads, hper;  // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
-    int ws;           // 4 heads: the workspace values of one row
-};
-
-// the arguments of head h alone: every operand moved to that head's slice, the workspace to that head's values of row 0
-template <typename VT>
-__device__ __forceinline__ AttBwdArgs<VT> bwd_head(const AttBwdArgs<VT> &A, const int h)
-{
-    AttBwdArgs<VT> H = A;
-    const size_t ok = (size_t)h * A.k, od = (size_t)h * A.d;
-    H.Q += ok;
-    H.K += ok;
-    H.V += od;
-    H.dO += od;
-    if (H.dQ)
-        H.dQ += ok;
-    if (H.dK)
-        H.dK += ok;
-    if (H.dV)
-        H.dV += od;
-    if (H.work)
-        H.work += 4 * (size_t)h;
-    return H;
-}
-
-// s_e and dp_e of the entry (i, j)
-template <typename VT, bool VEC>
-__device__ __forceinline__ void bwd_entry(const AttBwdArgs<VT> &A, const size_t i, const size_t j, VT &s, VT &dp)
-{
-    s = att_score<VT, VEC>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
-    dp = att_score<VT, VEC>(A.dO + i * A.lddo, A.V + j * A.ldv, A.d);
-}
-
-// p_e and ds_e of the entry (i, j) from the workspace values of row i: the column kernel's entry
-template <typename VT, bool VEC>
-__device__ __forceinline__ void bwd_entry_col(const AttBwdArgs<VT> &A, const size_t i, const size_t j, VT &p, VT &ds)
-{
-    const VT *wk = A.work + (size_t)A.ws * i;
-    const VT M = wk[0], r = wk[1], D = wk[2];
-    VT s, dp;
-    bwd_entry<VT, VEC>(A, i, j, s, dp);
-    p = exp_vt(s - M) * r;
-    ds = p * (dp - D);
-}
-
-// ---- accumulation, L <= 16: ONE chain per output column over the entries in ascending order.  coef / idx: lane sub * 16 + e
-// holds the coefficient and the operand row of entry e; out: the output row (used where rowok)
-template <typename VT>
-__device__ __forceinline__ void bwd_short_acc(const bool rowok, const int rl, const int sub, const int pos, const VT coef, const int idx,
-                                              const VT *__restrict__ X, const int ldx, const int width, VT *out)
-{
-    constexpr int G = AT_G;
-    for (int cb = 0; cb < width; cb += G) { // (uniform)
-        const int c = cb + pos;
-        VT acc = (VT)0;
-        for (int e = 0; e < G; e++) {
-            if (!__any(rowok && e < rl)) // (uniform: the shuffles below are executed by every lane)
-                break;
-            const VT we = __shfl(coef, sub * G + e, OMEGA);
-            const int je = __shfl(idx, sub * G + e, OMEGA);
-            if (rowok && e < rl && c < width)
-                acc = fma_vt(we, X[(size_t)(uint32_t)je * ldx + c], acc);
-        }
-        if (rowok && c < width)
-            out[c] = acc;
-    }
-}
-
-// ---- accumulation, 17 <= L <= 512: the forward's wavefront rule; coef / idx: the wavefront's staged entries in LDS
-template <typename VT>
-__device__ __forceinline__ void bwd_wave_acc(const VT *coef, const int *idx, const int rl, const VT *__restrict__ X, const int ldx,
-                                             const int width, VT *out)
-{
-    const int lane = threadIdx.x & (OMEGA - 1);
-    for (int cb = 0; cb < width; cb += OMEGA) {
-        const int wb = width - cb < OMEGA ? width - cb : OMEGA;
-        const int C = att_pow2(wb), S = OMEGA / C;
-        const int slot = lane / C, cc = lane & (C - 1);
-        VT acc = (VT)0;
-        if (cc < wb) {
-            const VT *x = X + cb + cc;
-#pragma unroll 4
-            for (int e = slot; e < rl; e += S)
-                acc = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], acc);
-        }
-        for (int off = C; off < OMEGA; off <<= 1) // (uniform; adjacent slots first)
-            acc += __shfl_xor(acc, off, OMEGA);
-        if (slot == 0 && cc < wb)
-            out[cb + cc] = acc;
-    }
-}
-
-// ---- accumulation, L > 512: the forward's workgroup rule.  staged: coef / idx hold all rl entries (filled by the caller; the
-// barrier below publishes them); otherwise fill(base, n) writes entries base .. base + n - 1 to coef / idx [0, n) chunk by chunk,
-// again for every 256 output columns.  Ends with a barrier: the stage is free.
-template <typename VT, typename FILL>
-__device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FILL fill, const VT *coef, const int *idx,
-                                            const VT *__restrict__ X, const int ldx, const int width, VT *out, VT *red)
-{
-    const int tid = (int)threadIdx.x;
-    for (int cg = 0; cg < width; cg += OMEGA * AT_HUB_BLOCKS) {
-        VT acc[AT_HUB_BLOCKS];
-#pragma unroll
-        for (int b = 0; b < AT_HUB_BLOCKS; b++)
-            acc[b] = (VT)0;
-        for (int base = 0; base < rl; base += AT_STAGE) {
-            const int n = rl - base < AT_STAGE ? rl - base : AT_STAGE;
-            if (!staged) {
-                __syncthreads(); // (the stage is free: the previous chunk has been read)
-                fill(base, n);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int b = 0; b < AT_HUB_BLOCKS; b++) {
-                const int cb = cg + b * OMEGA;
-                if (cb < width) {
-                    const int wb = width - cb < OMEGA ? width - cb : OMEGA;
-                    const int C = att_pow2(wb), S = AT_BLOCK / C; // (AT_STAGE is a multiple of S: a chunk keeps j mod S)
-                    const int slot = tid / C, cc = tid & (C - 1);
-                    if (cc < wb) {
-                        const VT *x = X + cb + cc;
-                        VT o = acc[b];
-#pragma unroll 4
-                        for (int e = slot; e < n; e += S)
-                            o = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], o);
-                        acc[b] = o;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < AT_HUB_BLOCKS; b++) {
-            const int cb = cg + b * OMEGA;
-            if (cb < width) { // (uniform)
-                const int wb = width - cb < OMEGA ? width - cb : OMEGA;
-                const int C = att_pow2(wb);
-                VT o = acc[b];
-                for (int off = C; off < OMEGA; off <<= 1) // adjacent slots of the wavefront first ...
-                    o += __shfl_xor(o, off, OMEGA);
-                red[tid] = o;
-                __syncthreads();
-                if (tid < wb) // ... then (w0 + w1) + (w2 + w3); lane c < C of every wavefront holds column c
-                    out[cb + tid] = (red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid]);
-                __syncthreads(); // (red is free for the next block)
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// ---- lines of at most 16 entries (empty ones included): 16 lanes per line, 4 lines of the wavefront per pass ---------------
-template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_short(const AttBwdArgs<VT> &A0, const long long row0, const int len, const int t0, const int rem0,
-                                          const int h0, const int h1)
-{
-    constexpr int G = AT_G, ROWS = OMEGA / G;
-    const int lane = threadIdx.x & (OMEGA - 1);
-    const int sub = lane / G, pos = lane % G;
-    const unsigned long long cls = __ballot(len >= 0 && len <= G); // (len = -1: no such line)
-    if (!cls)
-        return;
-    for (int pass = 0; pass < G; pass++) {
-        const unsigned long long here = (cls >> (pass * ROWS)) & ((1ull << ROWS) - 1);
-        if (!here) // (wave-uniform)
-            continue;
-        const int src = pass * ROWS + sub;
-        const int rl = __shfl(len, src, OMEGA);
-        const int rt0 = __shfl(t0, src, OMEGA);
-        const int rrem = __shfl(rem0, src, OMEGA);
-        const bool rowok = (cls >> src) & 1;
-        const bool act = rowok && pos < rl;
-        const size_t r = (size_t)(row0 + src);
-        int other = 0; // the lane's column: loaded once, kept across the heads
-        if (act)
-            other = A0.col[att_storage(A0, rt0, rrem, pos)];
-        for (int h = h0; h < h1; h++) { // (uniform)
-            const AttBwdArgs<VT> A = bwd_head(A0, h);
-            if constexpr (COL) {
-                VT p = (VT)0, ds = (VT)0;
-                if (act)
-                    bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, p, ds);
-                if (A.dV)
-                    bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
-                if (A.dK)
-                    bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
-            } else {
-                VT s = neg_inf<VT>(), dp = (VT)0;
-                if (act)
-                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, s, dp);
-                const VT mx = group_max<G>(s);
-                const VT w = act ? exp_vt(s - mx) : (VT)0;
-                const VT rinv = (VT)1 / group_sum<G>(w);
-                const VT p = act ? w * rinv : (VT)0;
-                const VT pg = p * dp;
-                const VT D = group_sum<G>(act ? pg : (VT)0);
-                const VT ds = act ? p * (dp - D) : (VT)0;
-                if (A.work && rowok && pos == 0) {
-                    VT *wk = A.work + (size_t)A.ws * r;
-                    wk[0] = mx;
-                    wk[1] = rinv;
-                    wk[2] = D;
-                }
-                if (A.dQ)
-                    bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
-            }
-        }
-    }
-}
-
-// ---- a line of 17 .. 512 entries: one wavefront; a / b / cl: the wavefront's 512 staged values, values and indices ---------
-// One head: A holds that head's slices; first: the head that stages cl, which the later heads read back (a lane its own entries).
-template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_wave_head(const AttBwdArgs<VT> &A, const bool first, const size_t r, const int rl, const int t0,
-                                              const int rem0, VT *a, VT *b, int *cl)
-{
-    const int lane = threadIdx.x & (OMEGA - 1);
-    if constexpr (COL) {
-        for (int j = lane; j < rl; j += OMEGA) {
-            const int i = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
-            VT p, ds;
-            bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
-            a[j] = p;
-            b[j] = ds;
-            cl[j] = i;
-        }
-        att_wave_sync();
-        if (A.dV)
-            bwd_wave_acc<VT>(a, cl, rl, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
-        if (A.dK)
-            bwd_wave_acc<VT>(b, cl, rl, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
-    } else {
-        VT mx = neg_inf<VT>();
-        for (int j = lane; j < rl; j += OMEGA) {
-            const int cj = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
-            VT s, dp;
-            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
-            a[j] = s;
-            b[j] = dp;
-            cl[j] = cj;
-            mx = max_vt(mx, s);
-        }
-        mx = wave_max(mx);
-        VT z = (VT)0;
-        for (int j = lane; j < rl; j += OMEGA) { // (a lane reads back what it stored itself, here and below)
-            const VT w = exp_vt(a[j] - mx);
-            a[j] = w;
-            z += w;
-        }
-        const VT rinv = (VT)1 / wave_sum(z);
-        VT dsum = (VT)0;
-        for (int j = lane; j < rl; j += OMEGA) {
-            const VT p = a[j] * rinv;
-            const VT pg = p * b[j];
-            a[j] = p;
-            dsum += pg;
-        }
-        const VT D = wave_sum(dsum);
-        for (int j = lane; j < rl; j += OMEGA)
-            a[j] = a[j] * (b[j] - D);
-        if (A.work && lane == 0) {
-            VT *wk = A.work + (size_t)A.ws * r;
-            wk[0] = mx;
-            wk[1] = rinv;
-            wk[2] = D;
-        }
-        att_wave_sync();
-        if (A.dQ)
-            bwd_wave_acc<VT>(a, cl, rl, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
-    }
-    att_wave_sync(); // (the next head's and the next line's entries stay behind these reads)
-}
-
-template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_wave_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
-                                              VT *b, int *cl, const int h0, const int h1)
-{
-    for (int h = h0; h < h1; h++) // (uniform)
-        bwd_wave_head<VT, VEC, COL>(bwd_head(A, h), h == h0, r, rl, t0, rem0, a, b, cl);
-}
-
-// ---- a line beyond 512 entries: the workgroup; a / b / cl: the AT_STAGE staged entries, red: AT_BLOCK values, red4: AT_WAVES
-// One head: A holds that head's slices; first: the head that stages cl of a line of at most AT_STAGE entries, which the later
-// heads read back (beyond AT_STAGE entries the stage holds one chunk at a time and every head walks the pattern again).
-template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_hub_head(const AttBwdArgs<VT> &A, const bool first, const size_t r, const int rl, const int t0,
-                                             const int rem0, VT *a, VT *b, int *cl, VT *red, VT *red4)
-{
-    const int tid = (int)threadIdx.x;
-    const bool staged = rl <= AT_STAGE; // (uniform over the workgroup, as every loop bound and barrier below)
-    if constexpr (COL) {
-        auto fill = [&](const int base, const int n) {
-            for (int jj = tid; jj < n; jj += AT_BLOCK) {
-                const int i = first || !staged ? A.col[att_storage(A, t0, rem0, base + jj)] : cl[jj];
-                VT p, ds;
-                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, p, ds);
-                a[jj] = p;
-                b[jj] = ds;
-                cl[jj] = i;
-            }
-        };
-        if (staged)
-            fill(0, rl);
-        if (A.dV)
-            bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.dO, A.lddo, A.d, A.dV + r * A.lddv, red);
-        if (A.dK)
-            bwd_hub_acc<VT>(rl, staged, fill, b, cl, A.Q, A.ldq, A.k, A.dK + r * A.lddk, red);
-    } else {
-        VT mx = neg_inf<VT>();
-        for (int j = tid; j < rl; j += AT_BLOCK) {
-            const int cj = first || !staged ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
-            VT s, dp;
-            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
-            if (staged) {
-                a[j] = s;
-                b[j] = dp;
-                cl[j] = cj;
-            }
-            mx = max_vt(mx, s);
-        }
-        mx = block_combine<VT, true>(wave_max(mx), red4);
-        VT z = (VT)0;
-        for (int j = tid; j < rl; j += AT_BLOCK) { // (a lane reads back what it stored itself, here and below)
-            VT s;
-            if (staged) {
-                s = a[j];
-            } else {
-                const int cj = A.col[att_storage(A, t0, rem0, j)];
-                s = att_score<VT, VEC>(A.Q + r * A.ldq, A.K + (size_t)(uint32_t)cj * A.ldk, A.k);
-            }
-            const VT w = exp_vt(s - mx);
-            if (staged)
-                a[j] = w;
-            z += w;
-        }
-        const VT rinv = (VT)1 / block_combine<VT, false>(wave_sum(z), red4);
-        VT dsum = (VT)0;
-        for (int j = tid; j < rl; j += AT_BLOCK) {
-            VT w, dp;
-            if (staged) {
-                w = a[j];
-                dp = b[j];
-            } else {
-                const int cj = A.col[att_storage(A, t0, rem0, j)];
-                VT s;
-                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
-                w = exp_vt(s - mx);
-            }
-            const VT p = w * rinv;
-            const VT pg = p * dp;
-            if (staged)
-                a[j] = p;
-            dsum += pg;
-        }
-        const VT D = block_combine<VT, false>(wave_sum(dsum), red4);
-        if (staged)
-            for (int j = tid; j < rl; j += AT_BLOCK)
-                a[j] = a[j] * (b[j] - D);
-        if (A.work && tid == 0) {
-            VT *wk = A.work + (size_t)A.ws * r;
-            wk[0] = mx;
-            wk[1] = rinv;
-            wk[2] = D;
-        }
-        auto fill = [&](const int base, const int n) {
-            for (int jj = tid; jj < n; jj += AT_BLOCK) {
-                const int cj = A.col[att_storage(A, t0, rem0, base + jj)];
-                VT s, dp;
-                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, s, dp);
-                const VT p = exp_vt(s - mx) * rinv;
-                a[jj] = p * (dp - D);
-                cl[jj] = cj;
-            }
-        };
-        if (A.dQ)
-            bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.K, A.ldk, A.k, A.dQ + r * A.lddq, red);
-        else
-            __syncthreads(); // (the stage is free for the next head or hub line)
-    }
-}
-
-template <typename VT, bool VEC, bool COL>
-__device__ __forceinline__ void bwd_hub_line(const AttBwdArgs<VT> &A, const size_t r, const int rl, const int t0, const int rem0, VT *a,
-                                             VT *b, int *cl, VT *red, VT *red4, const int h0, const int h1)
-{
-    for (int h = h0; h < h1; h++) // (uniform)
-        bwd_hub_head<VT, VEC, COL>(bwd_head(A, h), h == h0, r, rl, t0, rem0, a, b, cl, red, red4);
-}
-
-// MH: the packed multi-head call (blockIdx.y owns a contiguous group of heads); otherwise exactly one head, known at compile time
-template <typename VT, bool VEC, bool COL, bool MH>
-__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT> A)
-{
-    __shared__ VT a[AT_STAGE];
-    __shared__ VT b[AT_STAGE];
-    __shared__ int cl[AT_STAGE];
-    __shared__ VT red[AT_BLOCK];
-    __shared__ VT red4[AT_WAVES];
-    __shared__ int hub_n;
-    __shared__ int hub_row[AT_BLOCK];
-    if (threadIdx.x == 0)
-        hub_n = 0;
-    __syncthreads();
-
-    int h0 = 0, h1 = 1;
-    if constexpr (MH) {
-        h0 = (int)blockIdx.y * A.hper;
-        h1 = A.heads - h0 < A.hper ? A.heads : h0 + A.hper;
-    }
-    const int wave = (int)(threadIdx.x >> 6);
-    const long long row0 = (long long)blockIdx.x * AT_BLOCK + wave * OMEGA; // the wavefront's first line
-    const long long r = (long long)blockIdx.x * AT_BLOCK + threadIdx.x;
-    int first = 0, len = -1, t0 = 0, rem0 = 0;
-    if (r < A.lines) {
-        first = A.row_ptr[r];
-        len = A.row_ptr[r + 1] - first;
-        len = len < 0 ? 0 : len;
-        t0 = (int)((unsigned)first / (unsigned)A.T);
-        rem0 = first - t0 * A.T;
-    }
-    bwd_short<VT, VEC, COL>(A, row0, len, t0, rem0, h0, h1);
-
-    unsigned long long todo = __ballot(len > AT_G && len <= AT_WAVE_ROW);
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        bwd_wave_line<VT, VEC, COL>(A, (size_t)(row0 + src), __builtin_amdgcn_readlane(len, src), __builtin_amdgcn_readlane(t0, src),
-                                    __builtin_amdgcn_readlane(rem0, src), a + wave * AT_WAVE_ROW, b + wave * AT_WAVE_ROW,
-                                    cl + wave * AT_WAVE_ROW, h0, h1);
-    }
-
-    if (len > AT_WAVE_ROW)
-        hub_row[atomicAdd(&hub_n, 1)] = (int)threadIdx.x; // (an integer counter in LDS: the order of the list decides no bit)
-    __syncthreads(); // (and every wavefront is done with its share of the stage)
-    const int hubs = __builtin_amdgcn_readfirstlane(hub_n);
-    for (int i = 0; i < hubs; i++) { // (uniform over the workgroup: the barriers inside are reached by all)
-        const long long hr = (long long)blockIdx.x * AT_BLOCK + __builtin_amdgcn_readfirstlane(hub_row[i]);
-        const int ra = __builtin_amdgcn_readfirstlane(A.row_ptr[hr]);
-        const int rl = __builtin_amdgcn_readfirstlane(A.row_ptr[hr + 1]) - ra;
-        const int ht0 = (int)((unsigned)ra / (unsigned)A.T);
-        bwd_hub_line<VT, VEC, COL>(A, (size_t)hr, rl, ht0, ra - ht0 * A.T, a, b, cl, red, red4, h0, h1);
-    }
-}
-
-// groups: the head groups over grid.y, 0 for the rule (att_heads_per_group of this side's line count)
-template <typename VT, bool COL>
-static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, AttBwdArgs<VT> A, const int groups, const bool vec,
-                                     hipStream_t s)
-{
-    if (g.m <= 0 || A.heads <= 0)
-        return hipSuccess;
-    A.lines = g.m;
-    A.hper = groups > 0 ? (A.heads + groups - 1) / groups : att_heads_per_group(g.m, A.heads);
-    A.sigma = g.sigma > 0 ? g.sigma : 1;
-    A.T = g.tile_elems > 0 ? g.tile_elems : OMEGA;
-    A.tiles = g.p > 1 ? g.p - 1 : 0;
-    A.recip = (1u << 20) / (unsigned)A.sigma + 1u;
-    A.row_ptr = d.row_ptr;
-    A.col = d.col;
-    A.tile_ptr = d.tile_ptr;
-    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 block(AT_BLOCK);
-    if (A.heads == 1) {
-        const dim3 grid(blocks);
-        if (vec)
-            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, false>), grid, block, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, false>), grid, block, 0, s, A);
-    } else {
-        const dim3 grid(blocks, (unsigned)((A.heads + A.hper - 1) / A.hper));
-        if (vec)
-            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, true>), grid, block, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, true>), grid, block, 0, s, A);
-    }
-    return hipGetLastError();
-}
 
 // g / d: the parent's pattern (the row kernel); gt / dt: the transposed companion's (the column kernel, only when dK or dV is
 // wanted: null otherwise).  The row kernel runs when dQ is wanted or the column kernel needs the workspace.
@@ -555,13 +67,7 @@ static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, 
     A.lddq = lddq;
     A.lddk = lddk;
     A.lddv = lddv;
-    // 16-byte loads: every head's slice of every row of Q, K, V and dO starts on a 16-byte boundary (a chain shorter than one
-    // block of 32 bytes takes element loads anyway)
-    bool vec = heads == 1 || (((size_t)k * sizeof(VT)) % 16 == 0 && ((size_t)dcols * sizeof(VT)) % 16 == 0);
-    const void *ptrs[4] = {Q, K, V, dO};
-    const int lds[4] = {ldq, ldk, ldv, lddo};
-    for (int i = 0; i < 4; i++)
-        vec = vec && reinterpret_cast<uintptr_t>(ptrs[i]) % 16 == 0 && ((size_t)lds[i] * sizeof(VT)) % 16 == 0;
+    const bool vec = attention_bwd_vec<VT>(heads, k, dcols, Q, ldq, K, ldk, V, ldv, dO, lddo);
     const bool column = gt && dt && (dK || dV);
     hipError_t e = hipSuccess;
     if (dQ || column) {

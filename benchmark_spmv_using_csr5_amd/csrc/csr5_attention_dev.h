@@ -90,6 +90,26 @@ __device__ __forceinline__ VT att_score(const VT *__restrict__ q, const VT *__re
     return acc;
 }
 
+// The additive score bias of the biased entry points (csr5hip_mha_biased and its backward).  val: the value array, in tile order,
+// of the handle whose pattern the kernel walks -- the parent's in the row kernels, the transposed companion's in the column
+// kernel -- read at the storage position the entry's column is read from.  slopes: one value per head, or null (b = a, no
+// multiplication).  c: the scale, converted once to the value type.
+template <typename VT>
+struct AttBias {
+    const VT *val;
+    const VT *slopes;
+    VT c;
+};
+
+// the biased score of head h from the chain's qk and the entry's value a, every operation its own rounding:
+// b = slope_h * a (one multiplication; b = a without slopes), s = fma(qk, c, b)
+template <typename VT>
+__device__ __forceinline__ VT att_bias_score(const AttBias<VT> &B, const int h, const VT qk, const VT a)
+{
+    const VT b = B.slopes ? B.slopes[h] * a : a;
+    return fma_vt(qk, B.c, b);
+}
+
 // LDS written by some lanes of a wavefront is read by others of the same wavefront
 __device__ __forceinline__ void att_wave_sync()
 {

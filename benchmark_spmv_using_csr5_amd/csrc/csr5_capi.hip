@@ -1834,6 +1834,75 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads, const void *d_Q, int ldq, 
     return CSR5HIP_SUCCESS;
 }
 
+// csr5hip_mha with the score fma(qk, scale, slopes[h] * value of the entry) in one launch (csr5_attention_bias.hip): reads the
+// parent's tile-ordered values next to its columns and writes nothing of the handle; allocates nothing: enqueue-only.
+int csr5hip_mha_biased(csr5hip_handle h, int heads, double scale, const void *d_slopes, const void *d_Q, int ldq, const void *d_K, int ldk,
+                       int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
+{
+    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)heads * k, wd = (long long)heads * d;
+    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (heads == 0 || d == 0 || h->g.m <= 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_mha_biased(h->g, h->d, h->value_type, heads, 0, scale, d_slopes, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo,
+                              h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
+// csr5hip_mha_backward for those scores in two launches (csr5_attention_bwd_bias.hip): the row kernel reads the parent's values and
+// writes d_dS when it is given, the column kernel reads the transposed companion's.  Allocates nothing, changes nothing of the
+// handle or of its companion: enqueue-only.
+int csr5hip_mha_biased_backward(csr5hip_handle h, int heads, double scale, const void *d_slopes, const void *d_Q, int ldq, const void *d_K,
+                                int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo, void *d_dQ, int lddq,
+                                void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dS, int ldds)
+{
+    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)heads * k, wd = (long long)heads * d;
+    if (ldq < wk || ldk < wk || lddq < wk || lddk < wk || ldv < wd || lddo < wd || lddv < wd || (d_dS && ldds < heads))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
+    const bool any = d_dQ || column || d_dS;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (heads > 0 && any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (column && !h->at_built) {
+        g_last_error = "csr5hip_mha_biased_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (!any || heads == 0)
+        return CSR5HIP_SUCCESS;
+    const size_t vs = h->vsize();
+    if (nnz == 0 || (column && !h->at)) { // no entries (and then no companion arrays, and no element of dS): the zeros
+        if (d_dQ && k > 0 && h->g.m > 0)
+            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
+        if (d_dK && k > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
+        if (d_dV && d > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
+        return CSR5HIP_SUCCESS;
+    }
+    HIP_TRY(launch_mha_biased_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr, h->value_type, heads, 0, scale,
+                                  d_slopes, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work,
+                                  d_dS, ldds, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

@@ -265,6 +265,17 @@ hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const 
 hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type, int heads,
                           int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
                           const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
+// csr5_attention_bias.hip: launch_mha with the score s = fma(qk, (VT)scale, slopes[h] * a_e), a_e the value of the entry in d.val
+// (tile order: the position of its column); slopes: `heads` device values, or null (no multiplication).  d.val is only read
+hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale,
+                             const void *slopes, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
+                             void *O, int ldo, hipStream_t s);
+// csr5_attention_bwd_bias.hip: launch_mha_bwd for those scores; dQ and dK take ds * (VT)scale.  The row kernel reads d.val, the
+// column kernel dt->val; dS (null: not wanted): ds of entry e (CSR rank) and head h at dS[e * ldds + h], written by the row kernel
+hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
+                                 int heads, int groups, double scale, const void *slopes, const void *Q, int ldq, const void *K, int ldk,
+                                 int k, const void *V, int ldv, int dcols, const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk,
+                                 void *dV, int lddv, void *work, void *dS, int ldds, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

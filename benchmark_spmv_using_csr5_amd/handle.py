@@ -416,6 +416,97 @@ class anonymouslibHandle:
                                               int(d), _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV),
                                               int(lddv), _ptr(work))
 
+    # -- the same with a softmax scale and a score bias from the stored values (csr5hip.h csr5hip_mha_biased) -------
+    @staticmethod
+    def _mha_heads(Q) -> int:
+        """the head count Q announces (judged by ``_mha_args`` afterwards); 0 when Q is no 3-D tensor, which that check rejects"""
+        return int(Q.shape[1]) if hasattr(Q, "dim") and hasattr(Q, "shape") and Q.dim() == 3 else 0
+
+    def _mha_bias_args(self, who: str, heads: int, scale, slopes, dS, others):
+        """the checks of ``scale``, ``slopes`` and ``dS``, made before those of the operands: ValueError unless scale is a finite
+        number, slopes (or None) a contiguous 1-D GPU tensor of ``heads`` values of the handle's dtype, dS (or None) an
+        (nnz, heads) GPU tensor of that dtype with stride(1) == 1 and non-overlapping rows that shares storage with none of
+        ``others``.  Returns (scale, ldds)."""
+        import math
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+            raise ValueError(f"{who}: scale must be a finite Python number, not {scale!r}")
+        if slopes is not None:
+            if not hasattr(slopes, "data_ptr") or not hasattr(slopes, "is_contiguous"):
+                raise ValueError(f"{who}: slopes must be a torch tensor or None")
+            if str(slopes.dtype) != dt:
+                raise ValueError(f"{who}: slopes has dtype {slopes.dtype}, the handle holds {dt}")
+            if slopes.dim() != 1 or slopes.shape[0] != heads:
+                raise ValueError(f"{who}: slopes must have shape ({heads},), not {tuple(slopes.shape)}")
+            if not slopes.is_contiguous():
+                raise ValueError(f"{who}: slopes must be contiguous, not stride {slopes.stride()}")
+            if slopes.device.type != "cuda":
+                raise ValueError(f"{who}: slopes must live on the GPU, not {slopes.device}")
+        ldds = heads
+        if dS is not None:
+            if not hasattr(dS, "data_ptr") or not hasattr(dS, "stride"):
+                raise ValueError(f"{who}: dS must be a torch tensor or None")
+            if str(dS.dtype) != dt:
+                raise ValueError(f"{who}: dS has dtype {dS.dtype}, the handle holds {dt}")
+            if dS.dim() != 2 or tuple(dS.shape) != (self._nnz, heads):
+                raise ValueError(f"{who}: dS must have shape ({self._nnz}, {heads}), not {tuple(dS.shape)}")
+            if dS.numel() and heads > 1 and dS.stride(1) != 1:
+                raise ValueError(f"{who}: dS must have stride(1) == 1, not {dS.stride()}")
+            if dS.numel() and dS.shape[0] > 1 and dS.stride(0) < heads:
+                raise ValueError(f"{who}: dS rows overlap (stride(0) {dS.stride(0)} < heads = {heads})")
+            for name, t in others:
+                if hasattr(t, "untyped_storage") and dS.numel() and t.numel() and dS.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                    raise ValueError(f"{who}: dS shares a storage with {name} (views of one storage are rejected, disjoint or not)")
+            if dS.device.type != "cuda":
+                raise ValueError(f"{who}: dS must live on the GPU, not {dS.device}")
+            ldds = max(int(dS.stride(0)), heads) if dS.shape[0] > 1 and heads else heads
+        return float(scale), ldds
+
+    def mhaBiased(self, Q, K, V, O, scale=1.0, slopes=None) -> int:
+        """``mha`` on the scores ``scale * Q K^T + slopes[h] * A``: softmax scale and an additive bias from the handle's STORED
+        VALUES (what ``inputCSR`` gave or the last ``updateValues``), one value per stored entry, times a slope per head, in ONE
+        launch.  Per entry and head s = fma(qk, scale, slopes[h] * a), every operation rounded once; ``slopes=None`` takes the
+        value as it is.  A value of -Inf masks its entry.  Operands as ``mha``; ``scale`` is a finite Python number, ``slopes`` a
+        contiguous 1-D tensor of H values of the handle's dtype.  The handle's values are read, never written.  Anything else
+        raises ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        scale, _ = self._mha_bias_args("mhaBiased", self._mha_heads(Q), scale, slopes, None, ())
+        heads, k, d = self._mha_args("mhaBiased", ins, (("O", O, self._m, "d"),), None)
+        ld = self._mha_ld
+        return self.mha_biased_ptr(heads, scale, slopes, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def mha_biased_ptr(self, heads: int, scale: float, slopes, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
+        """csr5hip_mha_biased on raw device pointers (or tensors); slopes None for no slopes"""
+        return self._lib.csr5hip_mha_biased(self._h, int(heads), float(scale), _ptr(slopes), _ptr(Q), int(ldq), _ptr(K), int(ldk),
+                                            int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo))
+
+    def mhaBiasedBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None, scale=1.0, slopes=None, dS=None) -> int:
+        """the gradients of ``mhaBiased`` in TWO launches: operands, outputs and ``work`` as ``mhaBackward``, ``scale`` and
+        ``slopes`` as in the forward.  ``dS`` (optional): an (nnz, H) tensor with stride(1) == 1 that receives, per stored entry
+        in CSR order and head, the gradient for the biased score (before scale and slope); the gradient of the values is then
+        ``(dS * slopes).sum(1)`` and that of the slopes ``(dS * val[:, None]).sum(0)``.  dK and dV need ``work`` and the
+        transposed companion, dS and dQ neither.  The handle's values are read, never written.  Anything else raises ValueError
+        before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
+        scale, ldds = self._mha_bias_args("mhaBiasedBackward", self._mha_heads(Q), scale, slopes, dS, others)
+        heads, k, d = self._mha_args("mhaBiasedBackward", ins, outs, work)
+        ld = self._mha_ld
+        return self.mha_biased_backward_ptr(heads, scale, slopes, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
+                                            ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k, dV,
+                                            ld(dV) if dV is not None else heads * d, work, dS, ldds)
+
+    def mha_biased_backward_ptr(self, heads: int, scale: float, slopes, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO,
+                                lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dS, ldds: int) -> int:
+        """csr5hip_mha_biased_backward on raw device pointers (or tensors); None for an output that is not wanted"""
+        return self._lib.csr5hip_mha_biased_backward(self._h, int(heads), float(scale), _ptr(slopes), _ptr(Q), int(ldq), _ptr(K),
+                                                     int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO), int(lddo), _ptr(dQ),
+                                                     int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work), _ptr(dS),
+                                                     int(ldds))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

@@ -192,6 +192,27 @@ public:
                                          (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk, (void *)dV, lddv, (void *)work)
                   : _err;
     }
+    // extension: mha on the scores fma(qk, scale, slopes[h] * a), a the handle's stored value of the entry (read, never written);
+    // slopes: `heads` device values or null (csr5hip_mha_biased)
+    int mhaBiased(int heads, double scale, const ANONYMOUSLIB_VT *slopes, const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K,
+                  int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d, ANONYMOUSLIB_VT *O, int ldo)
+    {
+        return _h ? csr5hip_mha_biased(_h, heads, scale, (const void *)slopes, (const void *)Q, ldq, (const void *)K, ldk, k,
+                                       (const void *)V, ldv, d, (void *)O, ldo)
+                  : _err;
+    }
+    // extension: its gradients in two launches, operands as mhaBackward; dS (or null): nnz x heads values, the gradient for the biased
+    // score of entry e (CSR order) and head h at dS[e ldds + h] (csr5hip_mha_biased_backward)
+    int mhaBiasedBackward(int heads, double scale, const ANONYMOUSLIB_VT *slopes, const ANONYMOUSLIB_VT *Q, int ldq,
+                          const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d, const ANONYMOUSLIB_VT *dO,
+                          int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk, ANONYMOUSLIB_VT *dV, int lddv,
+                          ANONYMOUSLIB_VT *work, ANONYMOUSLIB_VT *dS, int ldds)
+    {
+        return _h ? csr5hip_mha_biased_backward(_h, heads, scale, (const void *)slopes, (const void *)Q, ldq, (const void *)K, ldk, k,
+                                                (const void *)V, ldv, d, (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk,
+                                                (void *)dV, lddv, (void *)work, (void *)dS, ldds)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

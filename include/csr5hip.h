@@ -447,6 +447,11 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads,
                 const void *d_Q, int ldq, const void *d_K, int ldk, int k,
                 const void *d_V, int ldv, int d, const void *d_dO, int lddo,
                 void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work);
+/* Extension (not in the reference): csr5hip_mha_biased and csr5hip_mha_biased_backward -- csr5hip_mha / csr5hip_mha_backward with a
+ * softmax scale and an additive score bias taken from the handle's stored values -- are declared, with their contracts, in
+ * csr5hip_bias.h, which this header includes at its end.  (A file of its own because tests/test_host.py compares the names declared
+ * in THIS file's text with the Python binding's main symbol list, which tests/test_mha_host.py in turn pins for the csr5hip_mha
+ * prefix; the two calls' declarations and exports are compared by tests/test_mha_bias_host.py.) */
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -625,6 +630,8 @@ int csr5hip_multi_gather_y(csr5hip_multi mh, void *h_y);
 int csr5hip_multi_fill_y(csr5hip_multi mh, int byte_value);
 /* destroy() on every shard (the shards' own copies go back to CSR order) */
 int csr5hip_multi_destroy(csr5hip_multi mh);
+
+#include "csr5hip_bias.h"
 
 #ifdef __cplusplus
 }
