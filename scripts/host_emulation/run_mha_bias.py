@@ -6,7 +6,7 @@ tests/zoo.py converted by the oracle WITH THEIR VALUES; for the backward the tra
 values in its own order, plays the transposed companion.
 
     python scripts/host_emulation/run_mha_bias.py [--matrices kat0,one-row,duplicates,aligned64,aligned1024,class-edges,class-edges^T,dealt]
-                                                  [--dtypes f64,f32] [--heads 1,3] [--kd 3x5,8x16] [--cxx clang++]
+                                                  [--dtypes f64,f32] [--heads 1,3] [--kd 3x5,8x16,12x8] [--skip kat0:12x8] [--cxx clang++]
 
 EVERY ENTRY'S VALUE IS DISTINCT (a permutation of nnz equidistant values in [-2, 2)), so a value taken from another entry's
 position -- in a moved tile, a fast-track tile, the CSR tail, a recompute sweep or on the column side -- is an error of order one.
@@ -20,6 +20,11 @@ Per matrix, precision, heads and (k, d), with scale 0.37 and a slope per head:
     ldds = heads + 2) and ONE group, and sigma = 16 with one group (16-byte loads where the slices allow them);
   * without slopes: the bits of slopes that are all one;
   * dQ and dS alone, without workspace and companion, have the bits they have with them.
+The shapes --kd is used with (SHAPES; any KxD is taken): (3, 5) element loads everywhere; (8, 16) and (12, 8) 16-byte loads where
+the configuration's leading dimensions allow them, with one head and with three (8, 12 and 16 values are a multiple of 16 bytes in
+either type, so every head's slice of every row is aligned); at 12 the fp32 chain is one block of 8 by 16-byte loads and 4
+elements.  (12, 8) is the shape tests/test_mha_bias_host.py runs under the sanitizers and tests/test_gpu_mha_bias_edges.py on the
+GPU.  The default is the first two.  --skip leaves (matrix, shape) pairs out of one run.
 Every array is an exact-size heap block.  This exercises the indexing, the row classes and the arithmetic of the source; it says
 nothing about the gfx950 build."""
 import argparse
@@ -43,6 +48,7 @@ from scripts.host_emulation.run_mha import build, same, wide  # noqa: E402
 DEFAULT = "kat0,one-row,duplicates,aligned64,aligned1024,class-edges,class-edges^T,dealt"
 HEADS = (1, 3)
 KD = ((3, 5), (8, 16))
+SHAPES = KD + ((12, 8),)
 CONFIGS = ((4, 16, False, 0), (7, 4, True, 1), (16, 7, False, 1))  # sigma, the companion's sigma, padded, head groups (0: the rule)
 SCALE = 0.37
 
@@ -145,11 +151,13 @@ def main():
     ap.add_argument("--dtypes", default="f64,f32")
     ap.add_argument("--heads", default=",".join(str(h) for h in HEADS))
     ap.add_argument("--kd", default=",".join(f"{k}x{d}" for k, d in KD), help="a subset lets the slow cases run side by side")
+    ap.add_argument("--skip", default="", help="NAME:KxD pairs to leave out, separated by commas")
     ap.add_argument("--cxx", default="/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else "clang++")
     args = ap.parse_args()
     dtypes = [{"f64": np.float64, "f32": np.float32}[t] for t in args.dtypes.split(",")]
     heads = [int(h) for h in args.heads.split(",")]
     kds = [tuple(int(v) for v in kd.split("x")) for kd in args.kd.split(",")]
+    skip = {tuple(pair.split(":")) for pair in args.skip.split(",") if pair}
     orc = Oracle()
     mats = matrices()
     with tempfile.TemporaryDirectory() as tmp:
@@ -168,6 +176,8 @@ def main():
                 u = float(np.finfo(dtype).eps) / 2
                 for H in heads:
                     for k, d in kds:
+                        if (name, f"{k}x{d}") in skip:
+                            continue
                         rng = np.random.default_rng(5)
                         Q = (rng.uniform(-1, 1, (mat.m, H, k)) * 2).astype(dtype)
                         K = rng.uniform(-1, 1, (mat.n, H, k)).astype(dtype)
