@@ -197,6 +197,17 @@ SYMBOLS_BIASED = [
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
 ]
 
+# the edge-bias attention calls, bound by load() like the others: heads, scale (double), B and ldb, then csr5hip_mha's /
+# csr5hip_mha_backward's arguments, the backward's followed by dB and lddb.  A list of their own for SYMBOLS_BIASED's reason: their
+# declarations are in include/csr5hip_edge_bias.h; tests/test_mha_edge_bias_host.py compares them with the exports.
+SYMBOLS_EDGE_BIAS = [
+    ("csr5hip_mha_edge_bias", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("csr5hip_mha_edge_bias_backward", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+]
+
 _lib = None
 
 
@@ -219,7 +230,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

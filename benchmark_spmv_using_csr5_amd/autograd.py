@@ -36,7 +36,9 @@ backward recomputes through ``attention`` and therefore DOES leave the handle as
 ``multihead_attention(A, Q, K, V)`` is ``fused_attention(..., backward="fused")`` for H heads at once on packed operands
 (rows, H, width): one ``A.mha`` forward, one ``A.mhaBackward`` backward, the handle untouched by both.  With ``scale``, ``bias``
 or ``slopes`` it computes ``softmax(scale Q K^T + slopes[h] bias)`` through ``A.mhaBiased`` / ``A.mhaBiasedBackward``: the bias is
-nnz values in CSR order and is given to the handle as ``spmm``'s ``val`` is, so the handle then holds it.
+nnz values in CSR order and is given to the handle as ``spmm``'s ``val`` is, so the handle then holds it.  A 2-D ``bias`` of
+shape (nnz, H) -- a learned edge bias that differs per head -- takes ``A.mhaEdgeBias`` / ``A.mhaEdgeBiasBackward`` instead: the
+bias stays the caller's tensor, the handle is given no values and nothing about it is recorded or checked.
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -352,6 +354,46 @@ class _BiasedMultiheadAttention(torch.autograd.Function):
         return (None,) + tuple(outs) + (None, grad_bias, grad_slopes)
 
 
+def _rows_packed(t):
+    """what mhaEdgeBias takes for B: (nnz, H) with stride(1) == 1 and non-overlapping rows; anything else is made contiguous"""
+    if (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return t.contiguous()
+
+
+class _EdgeBiasMultiheadAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        Bc = _rows_packed(bias.detach())
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.mhaEdgeBias(Qc, Kc, Vc, O, B=Bc, scale=scale), "mhaEdgeBias")
+        ctx.A, ctx.scale = A, scale
+        ctx.save_for_backward(Qc, Kc, Vc, Bc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        need = ctx.needs_input_grad[1:4]
+        need_bias = ctx.needs_input_grad[5]
+        if not (any(need) or need_bias):
+            return (None,) * 6
+        A = ctx.A
+        Q, K, V, B = ctx.saved_tensors
+        dO = _packed(dO.detach())
+        _on_current_stream(A, dO.device)
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
+        work = None
+        if need[1] or need[2]:
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        _check(A.mhaEdgeBiasBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaEdgeBiasBackward")
+        return (None,) + tuple(outs) + (None, dB)  # (dB IS the gradient of the bias: no reduction)
+
+
 def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     """``fused_attention`` for H heads in one call on packed operands: Q (m, H, k), K (n, H, k), V (n, H, d) -> (m, H, d); head h
     is, bit for bit, ``fused_attention(A, Q[:, h], K[:, h], V[:, h], backward="fused")``, in the output and in every gradient.
@@ -381,7 +423,20 @@ def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     Backward gives the handle the forward's bias again when another forward has replaced it in between.  Only when ``bias`` or
     ``slopes`` needs a gradient an (nnz, H) tensor of score gradients dS is allocated and written; ``grad_bias`` is
     ``(dS * slopes).sum(1)`` and ``grad_slopes`` ``(dS * bias[:, None]).sum(0)``, in torch.  Single-head users pass H = 1 on a
-    ``(rows, 1, width)`` view."""
+    ``(rows, 1, width)`` view.
+
+    A 2-D ``bias`` of shape (nnz, H), entry e in CSR order and head h at ``bias[e, h]``, is a PER-HEAD edge bias (a graph
+    transformer's ``Linear(edge_attr)``): the weights are ``softmax(scale * Q K^T + bias[:, h])`` by ONE ``A.mhaEdgeBias``
+    forward and ONE ``A.mhaEdgeBiasBackward`` backward.  The bias stays the caller's tensor: THE HANDLE IS GIVEN NO VALUES, its
+    values are not read, and nothing about it is recorded in forward or checked in backward, so none of the caveats above
+    applies.  ``grad_bias`` IS the (nnz, H) tensor dB the backward kernel writes -- allocated only when the bias needs a
+    gradient, no torch reduction applied.  ``slopes`` together with a 2-D bias raises ValueError: fold them into the bias
+    (``bias * slopes``).  A 1-D bias and ``bias=None`` are the code paths above, unchanged.  (Scale-only attention that does not
+    read the handle's values is ``A.mhaEdgeBias(B=None)``; this function has no keyword for it.)"""
+    if bias is not None and hasattr(bias, "dim") and bias.dim() == 2:
+        if slopes is not None:
+            raise ValueError("multihead_attention: slopes cannot be combined with a 2-D (nnz, H) bias: fold them into the bias")
+        return _EdgeBiasMultiheadAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias)
     if scale is None and bias is None and slopes is None:
         return _MultiheadAttention.apply(A, Q, K, V)
     if slopes is not None and bias is None and slopes.requires_grad and torch.is_grad_enabled():

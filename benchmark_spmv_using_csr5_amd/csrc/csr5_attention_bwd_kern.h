@@ -1,6 +1,7 @@
 // csr5_attention_bwd_kern.h -- the kernel templates of the attention backward on the pattern and the launcher of one side; the
 // contract is written out at the head of csr5_attention_bwd.hip.  Two translation units instantiate them: csr5_attention_bwd.hip
-// the plain entry points (AttBwdArgs), csr5_attention_bwd_bias.hip the biased one (csr5hip_mha_biased_backward; AttBwdBiasArgs).
+// the plain entry points (AttBwdArgs), csr5_attention_bwd_bias.hip the biased one (csr5hip_mha_biased_backward; AttBwdBiasArgs),
+// csr5_attention_bwd_edge.hip the edge-biased one (csr5hip_mha_edge_bias_backward; AttBwdEdgeArgs: ARGS::EDGE).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED), as in csr5_attention_kern.h: the plain instantiations
 // carry no argument, no branch and no load for it.  Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
 #pragma once
@@ -12,6 +13,7 @@ namespace csr5 {
 template <typename VT>
 struct AttBwdArgs {
     static constexpr bool BIASED = false;
+    static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's rank in the parent's CSR order)
     int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
     unsigned recip;
@@ -38,6 +40,19 @@ struct AttBwdBiasArgs : AttBwdArgs<VT> {
     int ldds;
 };
 
+// csr5hip_mha_edge_bias_backward: s = fma(qk, c, B[e * ldb + h]), e the entry's rank in the PARENT's CSR order: the position
+// walked in the row kernel (bias.map null), map[position walked] in the column kernel (bias.map the companion's source map), so
+// that an entry has the same s, p and ds on both sides.  dS / ldds are the call's dB / lddb: ds_e,h IS the gradient of B[e, h],
+// written by the row kernel by the biased rule.  Nothing of the handle's values is read.
+template <typename VT>
+struct AttBwdEdgeArgs : AttBwdArgs<VT> {
+    static constexpr bool BIASED = true;
+    static constexpr bool EDGE = true;
+    AttEdgeBias<VT> bias;
+    VT *dS;
+    int ldds;
+};
+
 // the arguments of head h alone: every operand moved to that head's slice, the workspace to that head's values of row 0 (biased:
 // the slopes and dS to that head's element, so that head 0 of the result is head h)
 template <typename ARGS>
@@ -57,7 +72,12 @@ __device__ __forceinline__ ARGS bwd_head(const ARGS &A, const int h)
         H.dV += od;
     if (H.work)
         H.work += 4 * (size_t)h;
-    if constexpr (ARGS::BIASED) {
+    if constexpr (ARGS::EDGE) {
+        if (H.bias.B)
+            H.bias.B += h;
+        if (H.dS)
+            H.dS += h;
+    } else if constexpr (ARGS::BIASED) {
         if (H.bias.slopes)
             H.bias.slopes += h;
         if (H.dS)
@@ -67,11 +87,14 @@ __device__ __forceinline__ ARGS bwd_head(const ARGS &A, const int h)
 }
 
 // biased: the value of the entry of rank j of a line, from the value array at the storage position its column is read from --
-// by every head again: unlike the columns the values are not staged; plain: nothing is read
+// by every head again: unlike the columns the values are not staged; plain: nothing is read.  Edge-biased: the bias of head 0 of
+// A of that entry, from B at the entry's rank in the parent's CSR order (the column kernel reads the map word first)
 template <typename VT, typename ARGS>
 __device__ __forceinline__ VT bwd_value(const ARGS &A, const int t0, const int rem0, const int j)
 {
-    if constexpr (ARGS::BIASED)
+    if constexpr (ARGS::EDGE)
+        return att_edge_value(A.bias, att_edge_rank(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j), 0);
+    else if constexpr (ARGS::BIASED)
         return A.bias.val[att_storage(A, t0, rem0, j)];
     else
         return (VT)0;
@@ -255,15 +278,23 @@ __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, 
         const bool rowok = (cls >> src) & 1;
         const bool act = rowok && pos < rl;
         const size_t r = (size_t)(row0 + src);
-        int other = 0; // the lane's column (and, biased, its value): loaded once, kept across the heads
+        int other = 0; // the lane's column (and, biased, its value; edge-biased, its rank): loaded once, kept across the heads
         VT av = (VT)0;
+        size_t er = 0;
         if (act)
             other = A0.col[att_storage(A0, rt0, rrem, pos)];
-        if constexpr (ARGS::BIASED)
+        if constexpr (ARGS::EDGE) {
+            if (act)
+                er = att_edge_rank(A0.bias, (size_t)rt0 * A0.T + (size_t)rrem + (size_t)pos);
+        } else if constexpr (ARGS::BIASED) {
             if (act)
                 av = bwd_value<VT>(A0, rt0, rrem, pos);
+        }
         for (int h = h0; h < h1; h++) { // (uniform)
             const ARGS A = bwd_head(A0, h);
+            if constexpr (ARGS::EDGE)
+                if (act)
+                    av = att_edge_value(A.bias, er, 0);
             if constexpr (COL) {
                 VT p = (VT)0, ds = (VT)0;
                 if (act)
@@ -565,6 +596,13 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd(const AttBwdArgs<VT>
 // the biased call is always the packed one (heads = 1 is a group of one head)
 template <typename VT, bool VEC, bool COL>
 __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_biased(const AttBwdBiasArgs<VT> A)
+{
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+
+// the edge-biased call likewise
+template <typename VT, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_edge(const AttBwdEdgeArgs<VT> A)
 {
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }

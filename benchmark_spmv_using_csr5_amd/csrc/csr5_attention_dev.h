@@ -110,6 +110,40 @@ __device__ __forceinline__ VT att_bias_score(const AttBias<VT> &B, const int h, 
     return fma_vt(qk, B.c, b);
 }
 
+// The additive score bias of the edge-bias entry points (csr5hip_mha_edge_bias and its backward): a caller-owned tensor in CSR
+// order, element (e, h) at B[e * ldb + h], e the entry's CSR rank in the PARENT's pattern; null: b = +0 and nothing is read.
+// map: null in the kernels that walk the parent's pattern, where an entry's position in the CSR order walked is its rank; in the
+// column kernel the transposed companion's source map (position in A^T's CSR -> position in A's CSR).  c: the scale, converted
+// once to the value type.  Nothing of the handle's values is read.
+template <typename VT>
+struct AttEdgeBias {
+    const VT *B;
+    const uint32_t *map;
+    int ldb;
+    VT c;
+};
+
+// the rank in the parent's CSR order of the entry at position q of the CSR order walked
+template <typename VT>
+__device__ __forceinline__ size_t att_edge_rank(const AttEdgeBias<VT> &E, const size_t q)
+{
+    return E.map ? (size_t)E.map[q] : q;
+}
+
+// the bias of head h of the entry of rank e
+template <typename VT>
+__device__ __forceinline__ VT att_edge_value(const AttEdgeBias<VT> &E, const size_t e, const int h)
+{
+    return E.B ? E.B[e * (size_t)E.ldb + (size_t)h] : (VT)0;
+}
+
+// the edge-biased score from the chain's qk and the entry's bias b: s = fma(qk, c, b), one rounding
+template <typename VT>
+__device__ __forceinline__ VT att_bias_score(const AttEdgeBias<VT> &E, const int, const VT qk, const VT b)
+{
+    return fma_vt(qk, E.c, b);
+}
+
 // LDS written by some lanes of a wavefront is read by others of the same wavefront
 __device__ __forceinline__ void att_wave_sync()
 {

@@ -1,6 +1,8 @@
 // csr5_attention_kern.h -- the kernel templates of the one-pass attention on the pattern and their typed launcher; the contract is
 // written out at the head of csr5_attention.hip.  Two translation units instantiate them: csr5_attention.hip the plain entry
-// points (csr5hip_attention, csr5hip_mha; AttArgs), csr5_attention_bias.hip the biased one (csr5hip_mha_biased; AttBiasArgs).
+// points (csr5hip_attention, csr5hip_mha; AttArgs), csr5_attention_bias.hip the biased one (csr5hip_mha_biased; AttBiasArgs),
+// csr5_attention_edge.hip the edge-biased one (csr5hip_mha_edge_bias; AttEdgeArgs: ARGS::EDGE, the bias from a caller's (nnz, heads)
+// tensor at the entry's CSR rank instead of from the handle's values).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED): the plain instantiations carry no bias argument,
 // no branch and no load for it -- their kernarg block and their code are those of the templates without it.
 // Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
@@ -13,6 +15,7 @@ namespace csr5 {
 template <typename VT>
 struct AttArgs {
     static constexpr bool BIASED = false;
+    static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's CSR rank)
     int m, k, d;
     int heads, hper;     // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 (tiles in tile order; beyond them the CSR tail)
@@ -30,6 +33,14 @@ template <typename VT>
 struct AttBiasArgs : AttArgs<VT> {
     static constexpr bool BIASED = true;
     AttBias<VT> bias;
+};
+
+// csr5hip_mha_edge_bias: s = fma(qk, c, B[e * ldb + h]), e the entry's CSR rank (att_edge_value); the handle's values are not read
+template <typename VT>
+struct AttEdgeArgs : AttArgs<VT> {
+    static constexpr bool BIASED = true;
+    static constexpr bool EDGE = true;
+    AttEdgeBias<VT> bias;
 };
 
 // ---- rows of at most 16 entries (empty rows included): 16 lanes per row, 4 rows of the wavefront per pass ------------------
@@ -54,12 +65,15 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
         const bool rowok = (cls >> src) & 1;
         const bool act = rowok && pos < rl;
         const size_t r = (size_t)(row0 + src);
-        int cj = 0; // the lane's column (and, biased, its value): loaded once, kept across the heads
+        int cj = 0; // the lane's column (and, biased, its value; edge-biased, its CSR rank): loaded once, kept across the heads
         VT av = (VT)0;
+        size_t er = 0;
         if (act) {
             const size_t st = att_storage(A, rt0, rrem, pos);
             cj = A.col[st];
-            if constexpr (ARGS::BIASED)
+            if constexpr (ARGS::EDGE)
+                er = (size_t)rt0 * A.T + (size_t)rrem + (size_t)pos;
+            else if constexpr (ARGS::BIASED)
                 av = A.bias.val[st];
         }
         for (int h = h0; h < h1; h++) { // (uniform)
@@ -68,7 +82,9 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
             VT s = neg_inf<VT>();
             if (act) {
                 s = att_score<VT, VEC>(A.Q + r * A.ldq + (size_t)h * A.k, A.K + (size_t)(uint32_t)cj * A.ldk + (size_t)h * A.k, A.k);
-                if constexpr (ARGS::BIASED)
+                if constexpr (ARGS::EDGE)
+                    s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, er, h));
+                else if constexpr (ARGS::BIASED)
                     s = att_bias_score(A.bias, h, s, av);
             }
             const VT mx = group_max<G>(s);
@@ -111,7 +127,9 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
                 cj = cl[j];
             }
             VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
-            if constexpr (ARGS::BIASED) // (the value is read again from the column's index by every head: it is not staged)
+            if constexpr (ARGS::EDGE) // (the bias is read from the entry's rank by every head: it is not staged either)
+                s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h));
+            else if constexpr (ARGS::BIASED) // (the value is read again from the column's index by every head: it is not staged)
                 s = att_bias_score(A.bias, h, s, A.bias.val[att_storage(A, t0, rem0, j)]);
             sc[j] = s;
             mx = max_vt(mx, s);
@@ -164,7 +182,9 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const V
         else
             cj = cl[j];
         VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
-        if constexpr (ARGS::BIASED)
+        if constexpr (ARGS::EDGE)
+            s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h));
+        else if constexpr (ARGS::BIASED)
             s = att_bias_score(A.bias, h, s, A.bias.val[att_storage(A, t0, rem0, j)]);
         if (staged) {
             sc[j] = s;
@@ -196,7 +216,10 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const V
                     const size_t st = att_storage(A, t0, rem0, base + jj);
                     const int cj = A.col[st];
                     VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
-                    if constexpr (ARGS::BIASED)
+                    if constexpr (ARGS::EDGE)
+                        s = att_bias_score(A.bias, h, s,
+                                           att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)(base + jj), h));
+                    else if constexpr (ARGS::BIASED)
                         s = att_bias_score(A.bias, h, s, A.bias.val[st]);
                     const VT w = exp_vt(s - mx);
                     sc[jj] = w;
@@ -319,6 +342,13 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention(const AttArgs<VT> A)
 // the biased call is always the packed one (heads = 1 is a group of one head)
 template <typename VT, bool VEC>
 __global__ void __launch_bounds__(AT_BLOCK) k_attention_biased(const AttBiasArgs<VT> A)
+{
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+
+// the edge-biased call likewise
+template <typename VT, bool VEC>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_edge(const AttEdgeArgs<VT> A)
 {
     CSR5_ATTENTION_KERNEL_BODY(true)
 }

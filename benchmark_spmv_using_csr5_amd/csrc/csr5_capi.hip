@@ -1903,6 +1903,76 @@ int csr5hip_mha_biased_backward(csr5hip_handle h, int heads, double scale, const
     return CSR5HIP_SUCCESS;
 }
 
+// csr5hip_mha with the score fma(qk, scale, B[e * ldb + h]), B a caller's tensor in CSR order, in one launch
+// (csr5_attention_edge.hip): reads the parent's pattern and nothing of its values; allocates nothing: enqueue-only.
+int csr5hip_mha_edge_bias(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq, const void *d_K,
+                          int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
+{
+    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)heads * k, wd = (long long)heads * d;
+    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd || (d_B && (long long)ldb < (long long)heads))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (heads == 0 || d == 0 || h->g.m <= 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_mha_edge(h->g, h->d, h->value_type, heads, 0, scale, d_B, ldb, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo,
+                            h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
+// csr5hip_mha_backward for those scores in two launches (csr5_attention_bwd_edge.hip): the row kernel reads B at the entry's CSR rank
+// and writes d_dB when it is given, the column kernel finds the rank through the companion's source map (b_at_map, passed, not
+// copied).  Reads nothing of the values, allocates nothing, changes nothing of the handle or of its companion: enqueue-only.
+int csr5hip_mha_edge_bias_backward(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq,
+                                   const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo,
+                                   void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dB, int lddb)
+{
+    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)heads * k, wd = (long long)heads * d;
+    if (ldq < wk || ldk < wk || lddq < wk || lddk < wk || ldv < wd || lddo < wd || lddv < wd ||
+        (d_B && (long long)ldb < (long long)heads) || (d_dB && (long long)lddb < (long long)heads))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
+    const bool any = d_dQ || column || d_dB;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (heads > 0 && any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (column && !h->at_built) {
+        g_last_error = "csr5hip_mha_edge_bias_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (!any || heads == 0)
+        return CSR5HIP_SUCCESS;
+    const size_t vs = h->vsize();
+    if (nnz == 0 || (column && (!h->at || !h->b_at_map.ptr))) { // no entries (and then no companion arrays, no element of dB): the zeros
+        if (d_dQ && k > 0 && h->g.m > 0)
+            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
+        if (d_dK && k > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
+        if (d_dV && d > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
+        return CSR5HIP_SUCCESS;
+    }
+    HIP_TRY(launch_mha_edge_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr,
+                                column ? (const uint32_t *)h->b_at_map.ptr : nullptr, h->value_type, heads, 0, scale, d_B, ldb, d_Q, ldq,
+                                d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work, d_dB, lddb, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------
 // The source map of the slab child, built from the parent's tile-ordered column_index: one allocation for the map, one -- released
 // again -- for the sort's temporaries, one synchronisation.  Nothing of the handle is modified before the map is complete.

@@ -276,6 +276,18 @@ hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, const
                                  int heads, int groups, double scale, const void *slopes, const void *Q, int ldq, const void *K, int ldk,
                                  int k, const void *V, int ldv, int dcols, const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk,
                                  void *dV, int lddv, void *work, void *dS, int ldds, hipStream_t s);
+// csr5_attention_edge.hip: launch_mha with the score s = fma(qk, (VT)scale, B[e * ldb + h]), e the entry's CSR rank; B: a caller's
+// nnz x heads device values, or null (b = +0, nothing read).  d.val is NOT read
+hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale, const void *B,
+                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
+                           int ldo, hipStream_t s);
+// csr5_attention_bwd_edge.hip: launch_mha_bwd for those scores; dQ and dK take ds * (VT)scale.  map: the companion's source map
+// (position in A^T's CSR -> position in A's), by which the column kernel finds an entry's row of B; dB (null: not wanted): ds of
+// entry e and head h at dB[e * lddb + h], written by the row kernel.  Neither d.val nor dt->val is read
+hipError_t launch_mha_edge_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const uint32_t *map,
+                               int value_type, int heads, int groups, double scale, const void *B, int ldb, const void *Q, int ldq,
+                               const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo, void *dQ,
+                               int lddq, void *dK, int lddk, void *dV, int lddv, void *work, void *dB, int lddb, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

@@ -507,6 +507,98 @@ class anonymouslibHandle:
                                                      int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work), _ptr(dS),
                                                      int(ldds))
 
+    # -- the same with a per-head bias from a caller-owned (nnz, H) tensor (csr5hip_edge_bias.h csr5hip_mha_edge_bias) -------
+    def _mha_edge_args(self, who: str, heads: int, scale, B, dB, others):
+        """the checks of ``scale``, ``B`` and ``dB``, made before those of the operands: ValueError unless scale is a finite
+        number and B and dB (or None) are 2-D GPU tensors of shape (nnz, heads) and of the handle's dtype with stride(1) == 1 and
+        non-overlapping rows; dB shares storage with none of ``others`` nor with B.  Returns (scale, ldb, lddb): the row strides."""
+        import math
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+            raise ValueError(f"{who}: scale must be a finite Python number, not {scale!r}")
+        lds = []
+        for name, t in (("B", B), ("dB", dB)):
+            if t is None:
+                lds.append(heads)
+                continue
+            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+                raise ValueError(f"{who}: {name} must be a torch tensor or None")
+            if str(t.dtype) != dt:
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+            if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
+                raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
+            if t.numel() and heads > 1 and t.stride(1) != 1:
+                raise ValueError(f"{who}: {name} must have stride(1) == 1, not {t.stride()}")
+            if t.numel() and t.shape[0] > 1 and t.stride(0) < heads:
+                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads = {heads})")
+            lds.append(max(int(t.stride(0)), heads) if t.shape[0] > 1 and heads else heads)
+        if dB is not None:
+            for name, t in others + (("B", B),):
+                if hasattr(t, "untyped_storage") and dB.numel() and t.numel() and dB.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                    raise ValueError(f"{who}: dB shares a storage with {name} (views of one storage are rejected, disjoint or not)")
+        for name, t in (("B", B), ("dB", dB)):
+            if t is not None and t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        return float(scale), lds[0], lds[1]
+
+    def _mha_edge_device(self, who: str, Q, named) -> None:
+        for name, t in named:
+            if t is not None and t.device != Q.device:
+                raise ValueError(f"{who}: {name} on {t.device}, Q on {Q.device}")
+
+    def mhaEdgeBias(self, Q, K, V, O, B=None, scale=1.0) -> int:
+        """``mha`` on the scores ``scale * Q K^T + B``: softmax scale and an additive bias that differs per stored entry AND per
+        head, from the caller's tensor ``B`` of shape (nnz, H) in CSR order (the order ``sddmm`` writes and ``updateValues``
+        takes), in ONE launch.  Per entry and head s = fma(qk, scale, B[e, h]), one rounding.  B has the handle's dtype and
+        stride(1) == 1; its row stride is free (a slice of a wider tensor is legal: the columns beyond H are never read).
+        ``B=None`` is no bias.  A bias of -Inf masks its entry in that head.  Operands as ``mha``.  THE HANDLE'S VALUES ARE NOT
+        READ and nothing of the handle changes.  Anything else raises ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        scale, ldb, _ = self._mha_edge_args("mhaEdgeBias", self._mha_heads(Q), scale, B, None, ())
+        heads, k, d = self._mha_args("mhaEdgeBias", ins, (("O", O, self._m, "d"),), None)
+        if B is not None and O.numel() and B.numel() and O.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
+            raise ValueError("mhaEdgeBias: O shares storage with B (aliased)")
+        self._mha_edge_device("mhaEdgeBias", Q, (("B", B),))
+        ld = self._mha_ld
+        return self.mha_edge_bias_ptr(heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def mha_edge_bias_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O,
+                          ldo: int) -> int:
+        """csr5hip_mha_edge_bias on raw device pointers (or tensors); B None for no bias"""
+        return self._lib.csr5hip_mha_edge_bias(self._h, int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq), _ptr(K),
+                                               int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo))
+
+    def mhaEdgeBiasBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None, B=None, scale=1.0, dB=None) -> int:
+        """the gradients of ``mhaEdgeBias`` in TWO launches: operands, outputs and ``work`` as ``mhaBackward``, ``B`` and ``scale``
+        as in the forward.  ``dB`` (optional): an (nnz, H) tensor with stride(1) == 1 that receives THE GRADIENT OF B, entry by
+        entry and head by head; no reduction is needed, and columns beyond H of a wider tensor it is a slice of stay untouched.
+        dK and dV need ``work`` and the transposed companion, dB and dQ neither.  The handle's values, the companion's included,
+        are not read.  Anything else raises ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
+        scale, ldb, lddb = self._mha_edge_args("mhaEdgeBiasBackward", self._mha_heads(Q), scale, B, dB, others)
+        heads, k, d = self._mha_args("mhaEdgeBiasBackward", ins, outs, work)
+        if B is not None:
+            for oname, o, _, _ in outs:
+                if o.numel() and B.numel() and o.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
+                    raise ValueError(f"mhaEdgeBiasBackward: {oname} shares storage with B (aliased)")
+        self._mha_edge_device("mhaEdgeBiasBackward", Q, (("B", B), ("dB", dB)))
+        ld = self._mha_ld
+        return self.mha_edge_bias_backward_ptr(heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
+                                               ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k,
+                                               dV, ld(dV) if dV is not None else heads * d, work, dB, lddb)
+
+    def mha_edge_bias_backward_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int,
+                                   dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int) -> int:
+        """csr5hip_mha_edge_bias_backward on raw device pointers (or tensors); None for B or for an output that is not wanted"""
+        return self._lib.csr5hip_mha_edge_bias_backward(self._h, int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq),
+                                                        _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO), int(lddo),
+                                                        _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
+                                                        _ptr(dB), int(lddb))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

@@ -213,6 +213,27 @@ public:
                                                 (void *)dV, lddv, (void *)work, (void *)dS, ldds)
                   : _err;
     }
+    // extension: mha on the scores fma(qk, scale, B[e ldb + h]), B the caller's nnz x heads device values in CSR order (e the entry's
+    // CSR rank) or null for no bias; the handle's values are not read (csr5hip_mha_edge_bias)
+    int mhaEdgeBias(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,
+                    const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d, ANONYMOUSLIB_VT *O, int ldo)
+    {
+        return _h ? csr5hip_mha_edge_bias(_h, heads, scale, (const void *)B, ldb, (const void *)Q, ldq, (const void *)K, ldk, k,
+                                          (const void *)V, ldv, d, (void *)O, ldo)
+                  : _err;
+    }
+    // extension: its gradients in two launches, operands as mhaBackward; dB (or null): nnz x heads values, the gradient of B, entry e
+    // and head h at dB[e lddb + h] (csr5hip_mha_edge_bias_backward)
+    int mhaEdgeBiasBackward(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,
+                            const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,
+                            const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk,
+                            ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work, ANONYMOUSLIB_VT *dB, int lddb)
+    {
+        return _h ? csr5hip_mha_edge_bias_backward(_h, heads, scale, (const void *)B, ldb, (const void *)Q, ldq, (const void *)K, ldk,
+                                                   k, (const void *)V, ldv, d, (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK,
+                                                   lddk, (void *)dV, lddv, (void *)work, (void *)dB, lddb)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

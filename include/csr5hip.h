@@ -452,6 +452,10 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads,
  * csr5hip_bias.h, which this header includes at its end.  (A file of its own because tests/test_host.py compares the names declared
  * in THIS file's text with the Python binding's main symbol list, which tests/test_mha_host.py in turn pins for the csr5hip_mha
  * prefix; the two calls' declarations and exports are compared by tests/test_mha_bias_host.py.) */
+/* Extension (not in the reference): csr5hip_mha_edge_bias and csr5hip_mha_edge_bias_backward -- csr5hip_mha / csr5hip_mha_backward with
+ * a softmax scale and a per-head additive score bias taken from a caller-owned (nnz, heads) tensor in CSR order, the handle's values
+ * left unread -- are declared, with their contracts, in csr5hip_edge_bias.h, which this header includes at its end for the same
+ * reason; their declarations and exports are compared by tests/test_mha_edge_bias_host.py. */
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -632,6 +636,7 @@ int csr5hip_multi_fill_y(csr5hip_multi mh, int byte_value);
 int csr5hip_multi_destroy(csr5hip_multi mh);
 
 #include "csr5hip_bias.h"
+#include "csr5hip_edge_bias.h"
 
 #ifdef __cplusplus
 }

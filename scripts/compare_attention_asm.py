@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Do the plain attention kernels still have the code they had?  Cross-compiles csr5_attention.hip and csr5_attention_bwd.hip for
-gfx950 to assembly (hipcc -O3 --cuda-device-only -S, once per value type) from a git revision and from the working tree, and
-compares every kernel of the revision (k_attention<..>, k_attention_bwd<..>) with the kernel of the same symbol now, instruction
-for instruction and register for register.  No GPU needed.
+"""Do the existing attention kernels still have the code they had?  Cross-compiles csr5_attention.hip, csr5_attention_bwd.hip and
+the two biased units (csr5_attention_bias.hip, csr5_attention_bwd_bias.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
+-S, once per value type) from a git revision and from the working tree, and compares every kernel of the revision
+(k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>) with the kernel of the same symbol
+now, instruction for instruction and register for register.  No GPU needed.
 
     python scripts/compare_attention_asm.py [--rev HEAD~1] [--keep DIR]
 
-The kernel templates are shared with the biased entry points (csr5_attention_kern.h, csr5_attention_bwd_kern.h, DESIGN.md section
-20), whose bodies are macros for exactly this property; run this after any edit of those headers.  Exit status 0: every kernel of
+The kernel templates are shared by the plain, the biased and the edge-biased entry points (csr5_attention_kern.h,
+csr5_attention_bwd_kern.h, DESIGN.md sections 20 and 21), whose bodies are macros for exactly this property; run this after any
+edit of those headers.  Exit status 0: every kernel of
 the revision is identical in the working tree; 1: some differ (their names and the number of differing lines are printed) or are
 missing.  Comment lines and trailing comments are ignored; nothing else is."""
 import argparse
@@ -21,7 +23,9 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join("benchmark_spmv_using_csr5_amd", "csrc")
 UNITS = (("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F32"),
-         ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F32"))
+         ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
+         ("csr5_attention_bias.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_bias.hip", "CSR5_ATTENTION_ONLY_F32"),
+         ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F32"))
 
 
 def kernels(tree, src, define, out):

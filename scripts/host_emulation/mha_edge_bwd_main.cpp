@@ -1,0 +1,66 @@
+// Stand-alone CPU run of csr5_attention_bwd_edge.hip's entry on the stand-in runtime of fake/hip/hip_runtime.h: reads a case file
+// written by run_mha_edge_bias.py (header; the scale; row_ptr, tile-ordered columns and tile_ptr of the matrix and of its
+// transpose; the source map (position in A^T's CSR -> position in A's CSR); B; packed Q, K, V, dO), writes dQ, dK, dV, dB.
+// launch_mha_edge_bwd with `heads` heads, `groups` head groups (0: the rule) and a workspace of exactly 4 m heads values.  THE
+// PATTERNS HAVE NO VALUE ARRAYS (null pointers).  B and dB are heap blocks of EXACTLY nnz ldb / nnz lddb values and the map one
+// of exactly nnz words: a wrong rank or map index is an access outside them, which -fsanitize=address reports.
+#include "csr5_attention_bwd_edge.hip"
+#include <cstdlib>
+struct Pattern {
+    int32_t *rp, *col;
+    uint32_t *tp;
+    csr5::Geometry g{};
+    csr5::DeviceArrays da{};
+    size_t read(FILE *f, int m, int n, int nnz, int sigma, int p)
+    {
+        rp = (int32_t *)malloc(4 * (size_t)(m + 1));
+        col = (int32_t *)malloc(4 * (size_t)(nnz ? nnz : 1));
+        tp = (uint32_t *)malloc(4 * (size_t)(p + 1));
+        g.m = m; g.n = n; g.nnz = nnz; g.sigma = sigma; g.p = p; g.tile_elems = 64 * sigma;
+        da.row_ptr = rp; da.col = col; da.tile_ptr = tp; da.val = nullptr;
+        return fread(rp, 4, m + 1, f) + fread(col, 4, nnz, f) + fread(tp, 4, p + 1, f);
+    }
+    void release() { free(rp); free(col); free(tp); }
+};
+int main(int argc, char **argv)
+{
+    if (argc < 3) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    int h[23];
+    double scale;
+    if (!f || fread(h, 4, 23, f) != 23 || fread(&scale, 8, 1, f) != 1) return 2;
+    const int m = h[0], n = h[1], nnz = h[2], sigma = h[3], p = h[4], sigma_t = h[5], p_t = h[6], k = h[7], d = h[8];
+    const int ldq = h[9], ldk = h[10], ldv = h[11], lddo = h[12], lddq = h[13], lddk = h[14], lddv = h[15], f64 = h[16], want = h[17];
+    const int heads = h[18], groups = h[19], has_b = h[20], ldb = h[21], lddb = h[22];
+    const size_t s = f64 ? 8 : 4;
+    Pattern A, At;
+    size_t got = A.read(f, m, n, nnz, sigma, p) + At.read(f, n, m, nnz, sigma_t, p_t);
+    auto block = [&](int rows, int ld) { return (char *)malloc(s * (size_t)rows * ld + ((size_t)rows * ld ? 0 : 8)); };
+    const size_t wn = 4 * (size_t)m * heads;
+    uint32_t *map = (uint32_t *)malloc(4 * (size_t)(nnz ? nnz : 1));
+    char *B = block(nnz, ldb);
+    char *Q = block(m, ldq), *K = block(n, ldk), *V = block(n, ldv), *dO = block(m, lddo);
+    char *dQ = block(m, lddq), *dK = block(n, lddk), *dV = block(n, lddv), *work = (char *)malloc(s * wn + 8), *dB = block(nnz, lddb);
+    got += fread(map, 4, nnz, f) + fread(B, s, (size_t)nnz * ldb, f);
+    got += fread(Q, s, (size_t)m * ldq, f) + fread(K, s, (size_t)n * ldk, f) + fread(V, s, (size_t)n * ldv, f) + fread(dO, s, (size_t)m * lddo, f);
+    fclose(f);
+    memset(dQ, 0xFF, s * (size_t)m * lddq); // NaN poison
+    memset(dK, 0xFF, s * (size_t)n * lddk);
+    memset(dV, 0xFF, s * (size_t)n * lddv);
+    memset(dB, 0xFF, s * (size_t)nnz * lddb);
+    memset(work, 0xFF, s * wn);
+    const bool column = want & 6;
+    const int rc = csr5::launch_mha_edge_bwd(A.g, A.da, column ? &At.g : nullptr, column ? &At.da : nullptr, column ? map : nullptr,
+                                             f64 ? CSR5HIP_F64 : CSR5HIP_F32, heads, groups, scale, has_b ? B : nullptr, ldb, Q, ldq, K, ldk,
+                                             k, V, ldv, d, dO, lddo, want & 1 ? dQ : nullptr, lddq, want & 2 ? dK : nullptr, lddk,
+                                             want & 4 ? dV : nullptr, lddv, column ? work : nullptr, want & 8 ? dB : nullptr, lddb, nullptr);
+    f = fopen(argv[2], "wb");
+    fwrite(dQ, s, (size_t)m * lddq, f);
+    fwrite(dK, s, (size_t)n * lddk, f);
+    fwrite(dV, s, (size_t)n * lddv, f);
+    fwrite(dB, s, (size_t)nnz * lddb, f);
+    fclose(f);
+    A.release(); At.release();
+    free(map); free(B); free(Q); free(K); free(V); free(dO); free(dQ); free(dK); free(dV); free(work); free(dB);
+    return rc;
+}

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Resource table of the SpMV kernels from hipcc's own -Rpass-analysis=kernel-resource-usage remarks.
 
-    python scripts/kernel_resources.py [--filter k_spmv] [--sigmas few|all] > profiles/rNN_resources.md
-Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
-VGPRs / SGPRs / scratch / LDS / occupancy in waves per SIMD.  Runs without a GPU."""
+    python scripts/kernel_resources.py [--filter k_spmv] [--sigmas few|all] [--units 'attention_(bwd_)?edge'] > profiles/rNN_resources.md
+Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_attention_edge.hip, csr5_attention_bwd_edge.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
+VGPRs / SGPRs / scratch / LDS / occupancy in waves per SIMD.  --units compiles only the translation units whose file name matches.
+Runs without a GPU."""
 import argparse
 import os
 import re
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--filter", default="k_spmv|k_spmm|k_sddmm|k_row_softmax|k_attention|k_slab|k_calibrate|k_range|k_x_permute|k_refresh|k_companion")
     ap.add_argument("--sigmas", default="few")
     ap.add_argument("--match", default=None, help="regex on the demangled name")
+    ap.add_argument("--units", default=None, help="regex on the source file name: compile only these translation units")
     args = ap.parse_args()
     rows = []
     for src, defs in (("csr5_spmv.hip", ["-DCSR5_SPMV_ONLY_F64"]), ("csr5_spmv.hip", ["-DCSR5_SPMV_ONLY_F32"]),
@@ -36,9 +38,14 @@ def main():
                       ("csr5_attention_bias.hip", ["-DCSR5_ATTENTION_ONLY_F64"]), ("csr5_attention_bias.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
                       ("csr5_attention_bwd_bias.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
                       ("csr5_attention_bwd_bias.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
+                      ("csr5_attention_edge.hip", ["-DCSR5_ATTENTION_ONLY_F64"]), ("csr5_attention_edge.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
+                      ("csr5_attention_bwd_edge.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
+                      ("csr5_attention_bwd_edge.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
                       ("csr5_slab.hip", []), ("csr5_hot.hip", []),
                       ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F64"]), ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F32"]),
                       ("csr5_companion.hip", [])):
+        if args.units and not re.search(args.units, src):
+            continue
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
                f"-I{ROOT}/include", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src),
                "-o", "/dev/null"] + defs + (["-DCSR5_FEW_SIGMAS"] if args.sigmas == "few" else [])
