@@ -208,6 +208,15 @@ SYMBOLS_EDGE_BIAS = [
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
 ]
 
+# the 16-bit-operand attention call, bound by load() like the others: the operand type, then csr5hip_mha_edge_bias's arguments.  A list
+# of its own for SYMBOLS_BIASED's reason: its declaration is in include/csr5hip_lowp.h; tests/test_mha_lowp_host.py compares it with the
+# export.  BF16 / F16: the operand types of that header (not handle value types).
+BF16, F16 = 2, 3
+SYMBOLS_LOWP = [
+    ("csr5hip_mha_lowp", C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+]
+
 _lib = None
 
 
@@ -230,7 +239,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -38,7 +38,9 @@ backward recomputes through ``attention`` and therefore DOES leave the handle as
 or ``slopes`` it computes ``softmax(scale Q K^T + slopes[h] bias)`` through ``A.mhaBiased`` / ``A.mhaBiasedBackward``: the bias is
 nnz values in CSR order and is given to the handle as ``spmm``'s ``val`` is, so the handle then holds it.  A 2-D ``bias`` of
 shape (nnz, H) -- a learned edge bias that differs per head -- takes ``A.mhaEdgeBias`` / ``A.mhaEdgeBiasBackward`` instead: the
-bias stays the caller's tensor, the handle is given no values and nothing about it is recorded or checked.
+bias stays the caller's tensor, the handle is given no values and nothing about it is recorded or checked.  With bf16 or fp16
+Q, K, V (and such a 2-D bias) the forward is one ``A.mhaLowp`` -- 16-bit operands, fp32 arithmetic, whatever the handle's dtype --
+and the backward widens what was kept and goes through ``A.mhaEdgeBiasBackward`` (a stopgap, see ``multihead_attention``).
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -394,6 +396,46 @@ class _EdgeBiasMultiheadAttention(torch.autograd.Function):
         return (None,) + tuple(outs) + (None, dB)  # (dB IS the gradient of the bias: no reduction)
 
 
+class _LowpMultiheadAttention(torch.autograd.Function):
+    """bf16 / fp16 operands: the forward is ONE ``A.mhaLowp``; the backward is a STOPGAP until there is a 16-bit backward kernel:
+    the saved operands and dO are widened to the handle's dtype, ``A.mhaEdgeBiasBackward`` computes the gradients there, and each
+    wanted one is cast to its input's dtype."""
+
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        Bc = _rows_packed(bias.detach()) if bias is not None else None
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.mhaLowp(Qc, Kc, Vc, O, B=Bc, scale=scale), "mhaLowp")
+        ctx.A, ctx.scale, ctx.has_bias = A, scale, Bc is not None
+        ctx.save_for_backward(*((Qc, Kc, Vc, Bc) if Bc is not None else (Qc, Kc, Vc)))
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        need = ctx.needs_input_grad[1:4]
+        need_bias = ctx.has_bias and ctx.needs_input_grad[5]
+        if not (any(need) or need_bias):
+            return (None,) * 6
+        A = ctx.A
+        low = ctx.saved_tensors[0].dtype
+        wide = torch.float64 if A._vt == _capi.F64 else torch.float32
+        Q, K, V = (t.to(wide) for t in ctx.saved_tensors[:3])  # (a temporary each: what the 16-bit backward kernel will save)
+        B = ctx.saved_tensors[3].to(wide) if ctx.has_bias else None
+        dO = _packed(dO.detach()).to(wide)
+        _on_current_stream(A, dO.device)
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
+        work = None
+        if need[1] or need[2]:
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            work = torch.empty(4 * A._m * Q.shape[1], dtype=wide, device=dO.device)
+        dB = torch.empty(tuple(B.shape), dtype=wide, device=dO.device) if need_bias else None
+        _check(A.mhaEdgeBiasBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaEdgeBiasBackward")
+        return (None,) + tuple(o.to(low) if o is not None else None for o in outs) + (None, dB.to(low) if dB is not None else None)
+
+
 def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     """``fused_attention`` for H heads in one call on packed operands: Q (m, H, k), K (n, H, k), V (n, H, d) -> (m, H, d); head h
     is, bit for bit, ``fused_attention(A, Q[:, h], K[:, h], V[:, h], backward="fused")``, in the output and in every gradient.
@@ -432,7 +474,19 @@ def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     applies.  ``grad_bias`` IS the (nnz, H) tensor dB the backward kernel writes -- allocated only when the bias needs a
     gradient, no torch reduction applied.  ``slopes`` together with a 2-D bias raises ValueError: fold them into the bias
     (``bias * slopes``).  A 1-D bias and ``bias=None`` are the code paths above, unchanged.  (Scale-only attention that does not
-    read the handle's values is ``A.mhaEdgeBias(B=None)``; this function has no keyword for it.)"""
+    read the handle's values is ``A.mhaEdgeBias(B=None)``; this function has no keyword for it.)
+
+    A ``torch.bfloat16`` or ``torch.float16`` Q takes the 16-BIT ROUTE, whatever the handle's dtype: K, V and ``bias`` (``None`` or
+    2-D (nnz, H)) have Q's dtype, forward is ONE ``A.mhaLowp`` -- fp32 arithmetic, O rounded once, the handle's values not read --
+    and Q, K, V and the bias are kept.  A 1-D bias or ``slopes`` raises ValueError there: those live in the handle's values, which
+    have another type.  BACKWARD IS A STOPGAP until a 16-bit backward kernel exists: the kept tensors and the incoming gradient are
+    widened to the handle's dtype, ONE ``A.mhaEdgeBiasBackward`` runs on them, and each wanted gradient is cast to its input's
+    dtype; on an fp32 handle the recomputed scores are the forward's bits.  There is no ``torch.autocast`` integration."""
+    if getattr(Q, "dtype", None) in (torch.bfloat16, torch.float16):
+        if slopes is not None or (bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2)):
+            raise ValueError("multihead_attention: with bf16 / fp16 operands the bias is None or a 2-D (nnz, H) tensor of their dtype; a "
+                             "1-D bias and slopes live in the handle's values, which have another type")
+        return _LowpMultiheadAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias)
     if bias is not None and hasattr(bias, "dim") and bias.dim() == 2:
         if slopes is not None:
             raise ValueError("multihead_attention: slopes cannot be combined with a 2-D (nnz, H) bias: fold them into the bias")

@@ -50,35 +50,46 @@ __device__ __forceinline__ size_t att_storage(const ARGS &A, const int t0, const
     return base + (size_t)i * OMEGA + l;
 }
 
-template <typename VT>
-__device__ __forceinline__ void att_load16(const VT *__restrict__ p, VT *o)
+// 16 bytes of a row of the storage type ST, converted to the compute type VT.  ST == VT: the words as they are; a 2-byte ST (bf16,
+// fp16; csr5_attention_lowp.hip): 8 elements, each widened exactly by the cast.
+template <typename ST, typename VT>
+__device__ __forceinline__ void att_load16(const ST *__restrict__ p, VT *o)
 {
     const uint4 w = *reinterpret_cast<const uint4 *>(p);
-    if constexpr (sizeof(VT) == 8) {
+    if constexpr (sizeof(ST) == 8) {
         o[0] = __builtin_bit_cast(double, (unsigned long long)w.y << 32 | w.x);
         o[1] = __builtin_bit_cast(double, (unsigned long long)w.w << 32 | w.z);
-    } else {
+    } else if constexpr (sizeof(ST) == 4) {
         o[0] = __builtin_bit_cast(float, w.x);
         o[1] = __builtin_bit_cast(float, w.y);
         o[2] = __builtin_bit_cast(float, w.z);
         o[3] = __builtin_bit_cast(float, w.w);
+    } else {
+        const unsigned words[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) { // (little endian: the element of the lower address in the lower half)
+            o[2 * j] = (VT)__builtin_bit_cast(ST, (unsigned short)(words[j] & 0xFFFFu));
+            o[2 * j + 1] = (VT)__builtin_bit_cast(ST, (unsigned short)(words[j] >> 16));
+        }
     }
 }
 
 // the chain of the definition over one row of Q and one of K.  VEC: blocks of 32 bytes by 16-byte loads, the rest by elements.
-template <typename VT, bool VEC>
-__device__ __forceinline__ VT att_score(const VT *__restrict__ q, const VT *__restrict__ kr, const int k)
+// ST: the type the rows are stored in, VT unless the caller's pointers say otherwise (csr5_attention_lowp.hip: bf16 / fp16 rows, the
+// chain in float); every element is widened by a cast, which is exact, and the chain runs c = 0, 1, 2, ... whatever the load width.
+template <typename VT, bool VEC, typename ST>
+__device__ __forceinline__ VT att_score(const ST *__restrict__ q, const ST *__restrict__ kr, const int k)
 {
-    constexpr int PER = 16 / (int)sizeof(VT);
+    constexpr int PER = 16 / (int)sizeof(ST);
     VT acc = (VT)0;
     int c = 0;
     if constexpr (VEC) {
         for (; c + 2 * PER <= k; c += 2 * PER) {
             VT a[2 * PER], b[2 * PER];
-            att_load16<VT>(q + c, a);
-            att_load16<VT>(q + c + PER, a + PER);
-            att_load16<VT>(kr + c, b);
-            att_load16<VT>(kr + c + PER, b + PER);
+            att_load16<ST>(q + c, a);
+            att_load16<ST>(q + c + PER, a + PER);
+            att_load16<ST>(kr + c, b);
+            att_load16<ST>(kr + c + PER, b + PER);
 #pragma unroll
             for (int j = 0; j < 2 * PER; j++)
                 acc = fma_vt(a[j], b[j], acc);
@@ -86,7 +97,7 @@ __device__ __forceinline__ VT att_score(const VT *__restrict__ q, const VT *__re
     }
 #pragma unroll 4
     for (; c < k; c++)
-        acc = fma_vt(q[c], kr[c], acc);
+        acc = fma_vt((VT)q[c], (VT)kr[c], acc);
     return acc;
 }
 
@@ -142,6 +153,42 @@ template <typename VT>
 __device__ __forceinline__ VT att_bias_score(const AttEdgeBias<VT> &E, const int, const VT qk, const VT b)
 {
     return fma_vt(qk, E.c, b);
+}
+
+// The same for 16-bit operands (csr5hip_mha_lowp, csr5_attention_lowp.hip): B is stored in the operand type ST (bf16 or fp16) and
+// widened exactly by the cast; c and the score are float.  The row kernels only: there is no map.
+template <typename ST>
+struct AttEdgeBiasLowp {
+    const ST *B;
+    int ldb;
+    float c;
+};
+
+template <typename ST>
+__device__ __forceinline__ float att_edge_value(const AttEdgeBiasLowp<ST> &E, const size_t e, const int h)
+{
+    return E.B ? (float)E.B[e * (size_t)E.ldb + (size_t)h] : 0.0f;
+}
+
+template <typename ST>
+__device__ __forceinline__ float att_bias_score(const AttEdgeBiasLowp<ST> &E, const int, const float qk, const float b)
+{
+    return fma_vt(qk, E.c, b);
+}
+
+// What a kernel stores of a computed value x: x itself where the storage type is the compute type; otherwise x rounded ONCE, to
+// nearest even, by the cast.  The empty asm keeps x, a float, whole in a register first: without it the compiler folds the
+// multiplication that produced x into the conversion (v_fma_mixlo_f16), which rounds the exact product to fp16 and skips the float
+// rounding -- a different number where the float product is a tie of the narrow type, and not the definition's.
+template <typename ST, typename VT>
+__device__ __forceinline__ ST att_stored(VT x)
+{
+    if constexpr (sizeof(ST) != sizeof(VT)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(x));
+#endif
+    }
+    return (ST)x;
 }
 
 // LDS written by some lanes of a wavefront is read by others of the same wavefront

@@ -3,6 +3,10 @@
 // points (csr5hip_attention, csr5hip_mha; AttArgs), csr5_attention_bias.hip the biased one (csr5hip_mha_biased; AttBiasArgs),
 // csr5_attention_edge.hip the edge-biased one (csr5hip_mha_edge_bias; AttEdgeArgs: ARGS::EDGE, the bias from a caller's (nnz, heads)
 // tensor at the entry's CSR rank instead of from the handle's values).
+// csr5_attention_lowp.hip instantiates them a fourth time with operands STORED in bf16 or fp16 and float arithmetic (csr5hip_mha_lowp;
+// AttLowpArgs, k_attention_lowp): ARGS::ST is the type behind the operand pointers, VT the type of everything computed.  Where
+// ST == VT the casts between them are no operation, and the kernels of the other units are, instruction for instruction, what they
+// were without them (scripts/compare_attention_asm.py).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED): the plain instantiations carry no bias argument,
 // no branch and no load for it -- their kernarg block and their code are those of the templates without it.
 // Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
@@ -16,6 +20,7 @@ template <typename VT>
 struct AttArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's CSR rank)
+    using ST = VT;                      // the type Q, K, V and O are stored in (AttLowpArgs: another one than the arithmetic's)
     int m, k, d;
     int heads, hper;     // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 (tiles in tile order; beyond them the CSR tail)
@@ -41,6 +46,28 @@ struct AttEdgeArgs : AttArgs<VT> {
     static constexpr bool BIASED = true;
     static constexpr bool EDGE = true;
     AttEdgeBias<VT> bias;
+};
+
+// csr5hip_mha_lowp (csr5_attention_lowp.hip): AttEdgeArgs<float>'s call with Q, K, V, B and O STORED in ST (bf16 or fp16).  The
+// arithmetic is float: the templates below widen an operand where they load it and round once where they store O, and are
+// otherwise the float instantiation's, statement for statement -- the result is the rounding of the float call's on the widened
+// operands.  A struct of its own: the existing ones keep their names and layouts, and their kernels their code.
+template <typename ST_>
+struct AttLowpArgs {
+    static constexpr bool BIASED = true;
+    static constexpr bool EDGE = true;
+    using ST = ST_;
+    int m, k, d;
+    int heads, hper;
+    int T, sigma, tiles;
+    unsigned recip;
+    const int32_t *row_ptr;
+    const int32_t *col;
+    const uint32_t *tile_ptr;
+    const ST *Q, *K, *V;
+    ST *O;
+    int ldq, ldk, ldv, ldo;
+    AttEdgeBiasLowp<ST> bias;
 };
 
 // ---- rows of at most 16 entries (empty rows included): 16 lanes per row, 4 rows of the wavefront per pass ------------------
@@ -77,8 +104,8 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
                 av = A.bias.val[st];
         }
         for (int h = h0; h < h1; h++) { // (uniform)
-            const VT *Vh = A.V + (size_t)h * A.d;
-            VT *Oh = A.O + (size_t)h * A.d;
+            const typename ARGS::ST *Vh = A.V + (size_t)h * A.d;
+            typename ARGS::ST *Oh = A.O + (size_t)h * A.d;
             VT s = neg_inf<VT>();
             if (act) {
                 s = att_score<VT, VEC>(A.Q + r * A.ldq + (size_t)h * A.k, A.K + (size_t)(uint32_t)cj * A.ldk + (size_t)h * A.k, A.k);
@@ -99,10 +126,10 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
                     const VT we = __shfl(w, sub * G + e, OMEGA);
                     const int je = __shfl(cj, sub * G + e, OMEGA);
                     if (rowok && e < rl && c < A.d)
-                        acc = fma_vt(we, Vh[(size_t)(uint32_t)je * A.ldv + c], acc);
+                        acc = fma_vt(we, (VT)Vh[(size_t)(uint32_t)je * A.ldv + c], acc);
                 }
                 if (rowok && c < A.d)
-                    Oh[r * A.ldo + c] = rl > 0 ? acc * rinv : (VT)0;
+                    Oh[r * A.ldo + c] = att_stored<typename ARGS::ST>(rl > 0 ? acc * rinv : (VT)0);
             }
         }
     }
@@ -115,8 +142,8 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
 {
     const int lane = threadIdx.x & (OMEGA - 1);
     for (int h = h0; h < h1; h++) { // (uniform) cl is staged by the first head and kept; sc is refilled per head
-        const VT *q = A.Q + r * A.ldq + (size_t)h * A.k;
-        const VT *Kh = A.K + (size_t)h * A.k;
+        const typename ARGS::ST *q = A.Q + r * A.ldq + (size_t)h * A.k;
+        const typename ARGS::ST *Kh = A.K + (size_t)h * A.k;
         VT mx = neg_inf<VT>();
         for (int j = lane; j < rl; j += OMEGA) { // (a lane reads back the columns it stored itself)
             int cj;
@@ -149,15 +176,15 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
             const int slot = lane / C, cc = lane & (C - 1);
             VT acc = (VT)0;
             if (cc < wb) {
-                const VT *v = A.V + (size_t)h * A.d + cb + cc;
+                const typename ARGS::ST *v = A.V + (size_t)h * A.d + cb + cc;
 #pragma unroll 4
                 for (int e = slot; e < rl; e += S)
-                    acc = fma_vt(sc[e], v[(size_t)(uint32_t)cl[e] * A.ldv], acc);
+                    acc = fma_vt(sc[e], (VT)v[(size_t)(uint32_t)cl[e] * A.ldv], acc);
             }
             for (int off = C; off < OMEGA; off <<= 1) // (uniform; adjacent slots first)
                 acc += __shfl_xor(acc, off, OMEGA);
             if (slot == 0 && cc < wb)
-                A.O[r * A.ldo + (size_t)h * A.d + cb + cc] = acc * rinv;
+                A.O[r * A.ldo + (size_t)h * A.d + cb + cc] = att_stored<typename ARGS::ST>(acc * rinv);
         }
         att_wave_sync(); // (the next head's and the next row's scores stay behind these reads)
     }
@@ -168,9 +195,9 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
 // the later heads take the columns from there.  (Beyond AT_STAGE entries the stage holds one chunk at a time and every head
 // walks the pattern again: keeping the chunk across the heads would take 4 accumulators per head and lane.)
 template <typename VT, bool VEC, typename ARGS>
-__device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const VT *q, const VT *Kh, const VT *Vh, VT *o_row,
-                                             const bool first, const int rl, const int t0, const int rem0, VT *sc, int *cl, VT *red,
-                                             VT *red4)
+__device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const typename ARGS::ST *q, const typename ARGS::ST *Kh,
+                                             const typename ARGS::ST *Vh, typename ARGS::ST *o_row, const bool first,
+                                             const int rl, const int t0, const int rem0, VT *sc, int *cl, VT *red, VT *red4)
 {
     const int tid = (int)threadIdx.x;
     const bool staged = rl <= AT_STAGE; // (uniform over the workgroup, as every loop bound and barrier below)
@@ -237,11 +264,11 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const V
                     const int C = att_pow2(wb), S = AT_BLOCK / C; // (AT_STAGE is a multiple of S: a chunk keeps j mod S)
                     const int slot = tid / C, cc = tid & (C - 1);
                     if (cc < wb) {
-                        const VT *v = Vh + cb + cc;
+                        const typename ARGS::ST *v = Vh + cb + cc;
                         VT o = acc[b];
 #pragma unroll 4
                         for (int e = slot; e < n; e += S)
-                            o = fma_vt(sc[e], v[(size_t)(uint32_t)cl[e] * A.ldv], o);
+                            o = fma_vt(sc[e], (VT)v[(size_t)(uint32_t)cl[e] * A.ldv], o);
                         acc[b] = o;
                     }
                 }
@@ -261,8 +288,8 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const V
                 red[tid] = o;
                 __syncthreads();
                 if (tid < wb) // ... then (w0 + w1) + (w2 + w3); lane c < C of every wavefront holds column c
-                    o_row[cb + tid] =
-                        ((red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid])) * rinv;
+                    o_row[cb + tid] = att_stored<typename ARGS::ST>(
+                        ((red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid])) * rinv);
                 __syncthreads(); // (red is free for the next block)
             }
         }
@@ -353,9 +380,24 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_edge(const AttEdgeArgs<V
     CSR5_ATTENTION_KERNEL_BODY(true)
 }
 
-// the pattern, the operands and the head groups of a launch.  groups: the head groups over grid.y, 0 for the rule
-template <typename VT>
-static void attention_fill(AttArgs<VT> &A, const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq,
+// 16-bit operands, float arithmetic: always the packed, edge-biased call.  7 waves per SIMD are k_attention_edge<float, ..>'s: left to
+// itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 75 registers (6 waves)
+#if defined(__HIP__)
+#define CSR5_ATT_LOWP_WAVES __attribute__((amdgpu_waves_per_eu(7)))
+#else // (the host emulation compiles this header as plain C++, where no function is a kernel)
+#define CSR5_ATT_LOWP_WAVES
+#endif
+template <typename ST, bool VEC>
+__global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_LOWP_WAVES k_attention_lowp(const AttLowpArgs<ST> A)
+{
+    using VT = float;
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+
+// the pattern, the operands and the head groups of a launch.  groups: the head groups over grid.y, 0 for the rule.  VT: the type
+// the operands are stored in
+template <typename VT, typename ARGS>
+static void attention_fill(ARGS &A, const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq,
                            const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo)
 {
     A.m = g.m;

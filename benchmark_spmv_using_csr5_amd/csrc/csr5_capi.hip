@@ -1929,6 +1929,35 @@ int csr5hip_mha_edge_bias(csr5hip_handle h, int heads, double scale, const void 
     return CSR5HIP_SUCCESS;
 }
 
+// csr5hip_mha_edge_bias on operands stored in bf16 / fp16, computed in float (csr5_attention_lowp.hip): reads the parent's pattern and
+// nothing of its values, so the handle's value type plays no part; allocates nothing: enqueue-only.
+int csr5hip_mha_lowp(csr5hip_handle h, int operand_type, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq,
+                     const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
+{
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
+        return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
+    if (heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)heads * k, wd = (long long)heads * d;
+    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd || (d_B && (long long)ldb < (long long)heads))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (heads == 0 || d == 0 || h->g.m <= 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_mha_lowp(h->g, h->d, operand_type, heads, 0, scale, d_B, ldb, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
 // csr5hip_mha_backward for those scores in two launches (csr5_attention_bwd_edge.hip): the row kernel reads B at the entry's CSR rank
 // and writes d_dB when it is given, the column kernel finds the rank through the companion's source map (b_at_map, passed, not
 // copied).  Reads nothing of the values, allocates nothing, changes nothing of the handle or of its companion: enqueue-only.

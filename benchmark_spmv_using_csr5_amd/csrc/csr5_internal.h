@@ -281,6 +281,11 @@ hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, const
 hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale, const void *B,
                            int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
                            int ldo, hipStream_t s);
+// csr5_attention_lowp.hip: launch_mha_edge on operands stored in 16 bits (operand_type: CSR5HIP_BF16 or CSR5HIP_F16, checked by the
+// caller; B, Q, K, V, O all of that type, leading dimensions in its elements), float arithmetic, O rounded once.  d.val is NOT read
+hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, int heads, int groups, double scale, const void *B,
+                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
+                           int ldo, hipStream_t s);
 // csr5_attention_bwd_edge.hip: launch_mha_bwd for those scores; dQ and dK take ds * (VT)scale.  map: the companion's source map
 // (position in A^T's CSR -> position in A's), by which the column kernel finds an entry's row of B; dB (null: not wanted): ds of
 // entry e and head h at dB[e * lddb + h], written by the row kernel.  Neither d.val nor dt->val is read

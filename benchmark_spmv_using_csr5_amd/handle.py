@@ -323,17 +323,18 @@ class anonymouslibHandle:
                                                     _ptr(work))
 
     # -- attention for all heads in one launch (csr5hip.h csr5hip_mha / csr5hip_mha_backward) -------
-    def _mha_args(self, who: str, ins, outs, work):
+    def _mha_args(self, who: str, ins, outs, work, dt=None):
         """the checks of ``attention``'s operands for packed 3-D tensors (rows, heads, width): ValueError, naming the operand,
         unless each has the handle's dtype, its row count, stride(2) == 1, stride(1) == width and rows that do not overlap; the
         head counts and widths agree; no output shares storage with an input, another output or ``work``; all live on one GPU.
-        Returns (heads, k, d)."""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        ``dt``: the dtype the operands must have instead of the handle's (``mhaLowp``: Q's).  Returns (heads, k, d)."""
+        holds = "the handle holds" if dt is None else "Q has"
+        dt = dt or ("torch.float64" if self._vt == _capi.F64 else "torch.float32")
         for name, t, rows, width in ins + outs:
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"{who}: {name} must be a torch tensor")
             if str(t.dtype) != dt:
-                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
             if t.dim() != 3 or t.shape[0] != rows:
                 raise ValueError(f"{who}: {name} must have shape ({rows}, heads, {width}), not {tuple(t.shape)}")
             if t.numel() and t.shape[2] > 1 and t.stride(2) != 1:
@@ -508,12 +509,14 @@ class anonymouslibHandle:
                                                      int(ldds))
 
     # -- the same with a per-head bias from a caller-owned (nnz, H) tensor (csr5hip_edge_bias.h csr5hip_mha_edge_bias) -------
-    def _mha_edge_args(self, who: str, heads: int, scale, B, dB, others):
+    def _mha_edge_args(self, who: str, heads: int, scale, B, dB, others, dt=None):
         """the checks of ``scale``, ``B`` and ``dB``, made before those of the operands: ValueError unless scale is a finite
         number and B and dB (or None) are 2-D GPU tensors of shape (nnz, heads) and of the handle's dtype with stride(1) == 1 and
-        non-overlapping rows; dB shares storage with none of ``others`` nor with B.  Returns (scale, ldb, lddb): the row strides."""
+        non-overlapping rows; dB shares storage with none of ``others`` nor with B.  ``dt``: the dtype B and dB must have instead
+        of the handle's (``mhaLowp``: Q's).  Returns (scale, ldb, lddb): the row strides."""
         import math
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        holds = "the handle holds" if dt is None else "Q has"
+        dt = dt or ("torch.float64" if self._vt == _capi.F64 else "torch.float32")
         if self._nnz is None:
             raise ValueError(f"{who}: call inputCSR first")
         if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
@@ -526,7 +529,7 @@ class anonymouslibHandle:
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"{who}: {name} must be a torch tensor or None")
             if str(t.dtype) != dt:
-                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+                raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
             if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
                 raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
             if t.numel() and heads > 1 and t.stride(1) != 1:
@@ -598,6 +601,37 @@ class anonymouslibHandle:
                                                         _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO), int(lddo),
                                                         _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
                                                         _ptr(dB), int(lddb))
+
+    # -- the forward with operands stored in bf16 / fp16, computed in fp32 (csr5hip_lowp.h csr5hip_mha_lowp) -------
+    _LOWP = {"torch.bfloat16": _capi.BF16, "torch.float16": _capi.F16}
+
+    def mhaLowp(self, Q, K, V, O, B=None, scale=1.0) -> int:
+        """``mhaEdgeBias`` on operands STORED IN 16 BITS: Q, K, V, O and B (when given) are all ``torch.bfloat16`` or all
+        ``torch.float16``, WHATEVER THE HANDLE'S DTYPE -- only its pattern is used, and an fp32 and an fp64 handle give the same
+        bits.  Everything is computed in fp32 and O is rounded once where it is stored, so the result is, bit for bit (NaN
+        payloads apart), ``mhaEdgeBias(Q.float(), K.float(), V.float(), O32, B.float(), scale)`` on an fp32 handle cast to the
+        operand type.  Layouts, strides, devices and aliasing as ``mhaEdgeBias``; ``B=None`` is no bias, a bias of -Inf masks its
+        entry in that head; an fp16 O is +-Inf where the fp32 result exceeds 65 504.  ONE launch; the handle is left untouched.
+        Anything else raises ValueError before the library is called."""
+        ot = self._LOWP.get(str(getattr(Q, "dtype", None)))
+        if ot is None:
+            raise ValueError(f"mhaLowp: Q must be a torch.bfloat16 or torch.float16 tensor, not {getattr(Q, 'dtype', type(Q).__name__)}")
+        dt = str(Q.dtype)
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        scale, ldb, _ = self._mha_edge_args("mhaLowp", self._mha_heads(Q), scale, B, None, (), dt)
+        heads, k, d = self._mha_args("mhaLowp", ins, (("O", O, self._m, "d"),), None, dt)
+        if B is not None and O.numel() and B.numel() and O.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
+            raise ValueError("mhaLowp: O shares storage with B (aliased)")
+        self._mha_edge_device("mhaLowp", Q, (("B", B),))
+        ld = self._mha_ld
+        return self.mha_lowp_ptr(ot, heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def mha_lowp_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int,
+                     d: int, O, ldo: int) -> int:
+        """csr5hip_mha_lowp on raw device pointers (or tensors): operand_type ``_capi.BF16`` or ``_capi.F16``, the leading
+        dimensions in elements of that type; B None for no bias"""
+        return self._lib.csr5hip_mha_lowp(self._h, int(operand_type), int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq),
+                                          _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo))
 
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:

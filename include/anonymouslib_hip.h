@@ -222,6 +222,13 @@ public:
                                           (const void *)V, ldv, d, (void *)O, ldo)
                   : _err;
     }
+    // extension: mhaEdgeBias on operands STORED in 16 bits -- operand_type CSR5HIP_BF16 or CSR5HIP_F16, whatever ANONYMOUSLIB_VT is; B, Q,
+    // K, V and O device pointers to that type, leading dimensions in its elements -- computed in fp32, O rounded once (csr5hip_mha_lowp)
+    int mhaLowp(int operand_type, int heads, double scale, const void *B, int ldb, const void *Q, int ldq, const void *K, int ldk, int k,
+                const void *V, int ldv, int d, void *O, int ldo)
+    {
+        return _h ? csr5hip_mha_lowp(_h, operand_type, heads, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, d, O, ldo) : _err;
+    }
     // extension: its gradients in two launches, operands as mhaBackward; dB (or null): nnz x heads values, the gradient of B, entry e
     // and head h at dB[e lddb + h] (csr5hip_mha_edge_bias_backward)
     int mhaEdgeBiasBackward(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,

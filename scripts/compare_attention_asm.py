@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Do the existing attention kernels still have the code they had?  Cross-compiles csr5_attention.hip, csr5_attention_bwd.hip and
-the two biased units (csr5_attention_bias.hip, csr5_attention_bwd_bias.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
+"""Do the existing attention kernels still have the code they had?  Cross-compiles csr5_attention.hip, csr5_attention_bwd.hip, the
+two biased units (csr5_attention_bias.hip, csr5_attention_bwd_bias.hip) and the two edge-biased ones (csr5_attention_edge.hip,
+csr5_attention_bwd_edge.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
 -S, once per value type) from a git revision and from the working tree, and compares every kernel of the revision
-(k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>) with the kernel of the same symbol
+(k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>, k_attention_edge<..>, k_attention_bwd_edge<..>) with the kernel of the same symbol
 now, instruction for instruction and register for register.  No GPU needed.
 
     python scripts/compare_attention_asm.py [--rev HEAD~1] [--keep DIR]
@@ -25,7 +26,9 @@ CSRC = os.path.join("benchmark_spmv_using_csr5_amd", "csrc")
 UNITS = (("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F32"),
          ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
          ("csr5_attention_bias.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_bias.hip", "CSR5_ATTENTION_ONLY_F32"),
-         ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F32"))
+         ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
+         ("csr5_attention_edge.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_edge.hip", "CSR5_ATTENTION_ONLY_F32"),
+         ("csr5_attention_bwd_edge.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_edge.hip", "CSR5_ATTENTION_BWD_ONLY_F32"))
 
 
 def kernels(tree, src, define, out):
