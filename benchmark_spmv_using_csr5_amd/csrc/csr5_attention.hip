@@ -67,65 +67,23 @@
 
 namespace csr5 {
 
-// heads == 1: the single-head instantiation.  groups: the head groups over grid.y, 0 for the rule (att_heads_per_group).
-template <typename VT>
-static hipError_t attention_typed(const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq, const void *K,
-                                  int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s)
-{
-    if (g.m <= 0 || dcols <= 0 || heads <= 0)
-        return hipSuccess;
-    AttArgs<VT> A;
-    attention_fill<VT>(A, g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo);
-    const bool vec = attention_vec<VT>(heads, Q, ldq, K, ldk, k);
-    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 block(AT_BLOCK);
-    if (heads == 1) {
-        const dim3 grid(blocks);
-        if (vec)
-            hipLaunchKernelGGL((k_attention<VT, true, false>), grid, block, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_attention<VT, false, false>), grid, block, 0, s, A);
-    } else {
-        const dim3 grid(blocks, (unsigned)((heads + A.hper - 1) / A.hper));
-        if (vec)
-            hipLaunchKernelGGL((k_attention<VT, true, true>), grid, block, 0, s, A);
-        else
-            hipLaunchKernelGGL((k_attention<VT, false, true>), grid, block, 0, s, A);
-    }
-    return hipGetLastError();
-}
-
-// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / -DCSR5_ATTENTION_ONLY_F32), as csr5_sddmm.hip.
+// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / _F32), as csr5_sddmm.hip:
+// each object holds the shared launcher's instantiation on its type, the fp64 one the dispatcher as well.
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_f64(const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq, const void *K, int ldk,
-                          int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s)
-{
-    return attention_typed<double>(g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
-}
+extern template AttLaunch attention_launch<AttArgs<float>>;
+template AttLaunch attention_launch<AttArgs<double>>;
 #endif
 #if !defined(CSR5_ATTENTION_ONLY_F64)
-hipError_t launch_mha_f32(const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq, const void *K, int ldk,
-                          int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s)
-{
-    return attention_typed<float>(g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
-}
+template AttLaunch attention_launch<AttArgs<float>>;
 #endif
 
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_f32(const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq, const void *K, int ldk,
-                          int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
-
-hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, const void *Q, int ldq,
-                      const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s)
+// heads == 1 is the single-head call: k_attention<VT, VEC, false>
+hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s)
 {
-    return value_type == CSR5HIP_F64 ? launch_mha_f64(g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s)
-                                     : launch_mha_f32(g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
-}
-
-hipError_t launch_attention(const Geometry &g, const DeviceArrays &d, int value_type, const void *Q, int ldq, const void *K, int ldk,
-                            int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s)
-{
-    return launch_mha(g, d, value_type, 1, 0, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
+    if (value_type == CSR5HIP_F64)
+        return attention_launch<AttArgs<double>>(g, d, c, s);
+    return attention_launch<AttArgs<float>>(g, d, c, s);
 }
 #endif
 

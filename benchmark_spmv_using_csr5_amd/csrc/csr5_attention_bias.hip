@@ -31,57 +31,22 @@
 
 namespace csr5 {
 
-// groups: the head groups over grid.y, 0 for the rule (att_heads_per_group)
-template <typename VT>
-static hipError_t attention_biased_typed(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *slopes,
-                                         const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
-                                         int ldo, hipStream_t s)
-{
-    if (g.m <= 0 || dcols <= 0 || heads <= 0)
-        return hipSuccess;
-    AttBiasArgs<VT> A;
-    attention_fill<VT>(A, g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo);
-    A.bias.val = (const VT *)d.val;
-    A.bias.slopes = (const VT *)slopes;
-    A.bias.c = (VT)scale;
-    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 grid(blocks, (unsigned)((heads + A.hper - 1) / A.hper)), block(AT_BLOCK);
-    if (attention_vec<VT>(heads, Q, ldq, K, ldk, k))
-        hipLaunchKernelGGL((k_attention_biased<VT, true>), grid, block, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_attention_biased<VT, false>), grid, block, 0, s, A);
-    return hipGetLastError();
-}
-
-// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / -DCSR5_ATTENTION_ONLY_F32), as csr5_attention.hip.
+// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / _F32), as csr5_sddmm.hip:
+// each object holds the shared launcher's instantiation on its type, the fp64 one the dispatcher as well.
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_biased_f64(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *slopes,
-                                 const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo,
-                                 hipStream_t s)
-{
-    return attention_biased_typed<double>(g, d, heads, groups, scale, slopes, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
-}
+extern template AttLaunch attention_launch<AttBiasArgs<float>>;
+template AttLaunch attention_launch<AttBiasArgs<double>>;
 #endif
 #if !defined(CSR5_ATTENTION_ONLY_F64)
-hipError_t launch_mha_biased_f32(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *slopes,
-                                 const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo,
-                                 hipStream_t s)
-{
-    return attention_biased_typed<float>(g, d, heads, groups, scale, slopes, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
-}
+template AttLaunch attention_launch<AttBiasArgs<float>>;
 #endif
 
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_biased_f32(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *slopes,
-                                 const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo,
-                                 hipStream_t s);
-
-hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale,
-                             const void *slopes, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                             void *O, int ldo, hipStream_t s)
+hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s)
 {
-    return value_type == CSR5HIP_F64 ? launch_mha_biased_f64(g, d, heads, groups, scale, slopes, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s)
-                                     : launch_mha_biased_f32(g, d, heads, groups, scale, slopes, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s);
+    if (value_type == CSR5HIP_F64)
+        return attention_launch<AttBiasArgs<double>>(g, d, c, s);
+    return attention_launch<AttBiasArgs<float>>(g, d, c, s);
 }
 #endif
 

@@ -43,92 +43,23 @@
 
 namespace csr5 {
 
-// g / d: the parent's pattern (the row kernel); gt / dt: the transposed companion's (the column kernel, only when dK or dV is
-// wanted: null otherwise).  The row kernel runs when dQ is wanted or the column kernel needs the workspace.
-template <typename VT>
-static hipError_t attention_bwd_typed(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads,
-                                      int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                                      const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work,
-                                      hipStream_t s)
-{
-    AttBwdArgs<VT> A{};
-    A.k = k;
-    A.d = dcols;
-    A.heads = heads;
-    A.ws = 4 * heads;
-    A.Q = (const VT *)Q;
-    A.K = (const VT *)K;
-    A.V = (const VT *)V;
-    A.dO = (const VT *)dO;
-    A.ldq = ldq;
-    A.ldk = ldk;
-    A.ldv = ldv;
-    A.lddo = lddo;
-    A.lddq = lddq;
-    A.lddk = lddk;
-    A.lddv = lddv;
-    const bool vec = attention_bwd_vec<VT>(heads, k, dcols, Q, ldq, K, ldk, V, ldv, dO, lddo);
-    const bool column = gt && dt && (dK || dV);
-    hipError_t e = hipSuccess;
-    if (dQ || column) {
-        AttBwdArgs<VT> R = A;
-        R.dQ = k > 0 ? (VT *)dQ : nullptr;
-        R.work = column ? (VT *)work : nullptr;
-        if (R.dQ || R.work)
-            e = attention_bwd_side<VT, false>(g, d, R, groups, vec, s);
-    }
-    if (e == hipSuccess && column) {
-        AttBwdArgs<VT> C = A;
-        C.dK = k > 0 ? (VT *)dK : nullptr;
-        C.dV = dcols > 0 ? (VT *)dV : nullptr;
-        C.work = (VT *)work;
-        if (C.dK || C.dV)
-            e = attention_bwd_side<VT, true>(*gt, *dt, C, groups, vec, s);
-    }
-    return e;
-}
-
-// The product build compiles this file once per value type (-DCSR5_ATTENTION_BWD_ONLY_F64 / _F32), as csr5_attention.hip.
+// The product build compiles this file once per value type (-DCSR5_ATTENTION_BWD_ONLY_F64 / _F32), as csr5_sddmm.hip:
+// each object holds the shared launcher's instantiation on its type, the fp64 one the dispatcher as well.
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
-hipError_t launch_mha_bwd_f64(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
-                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
-                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
-{
-    return attention_bwd_typed<double>(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV,
-                                       lddv, work, s);
-}
+extern template AttBwdLaunch attention_bwd_launch<float, AttBwdArgs<float>>;
+template AttBwdLaunch attention_bwd_launch<double, AttBwdArgs<double>>;
 #endif
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F64)
-hipError_t launch_mha_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
-                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
-                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
-{
-    return attention_bwd_typed<float>(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV,
-                                      lddv, work, s);
-}
+template AttBwdLaunch attention_bwd_launch<float, AttBwdArgs<float>>;
 #endif
 
 #if !defined(CSR5_ATTENTION_BWD_ONLY_F32)
-hipError_t launch_mha_bwd_f32(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int heads, int groups,
-                              const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
-                              int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
-
-hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type, int heads,
-                          int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                          const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
+// heads == 1 is the single-head call: k_attention_bwd<VT, VEC, COL, false>
+hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s)
 {
-    return value_type == CSR5HIP_F64 ? launch_mha_bwd_f64(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq,
-                                                          dK, lddk, dV, lddv, work, s)
-                                     : launch_mha_bwd_f32(g, d, gt, dt, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq,
-                                                          dK, lddk, dV, lddv, work, s);
-}
-
-hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
-                                const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
-                                int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s)
-{
-    return launch_mha_bwd(g, d, gt, dt, value_type, 1, 0, Q, ldq, K, ldk, k, V, ldv, dcols, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, work,
-                          s);
+    if (value_type == CSR5HIP_F64)
+        return attention_bwd_launch<double, AttBwdArgs<double>>(g, d, c, s);
+    return attention_bwd_launch<float, AttBwdArgs<float>>(g, d, c, s);
 }
 #endif
 

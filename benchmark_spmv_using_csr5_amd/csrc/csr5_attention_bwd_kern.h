@@ -607,6 +607,23 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_edge(const AttBwdEdg
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }
 
+// the kernels of an argument struct, as overloads (csr5_attention_kern.h attention_enqueue).  COL: the column kernel
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd<VT, VEC, COL, MH>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdBiasArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_biased<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdEdgeArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_edge<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+
 // the pattern walked and the head groups of one side's launch.  groups: the head groups over grid.y, 0 for the rule
 // (att_heads_per_group of this side's line count)
 template <typename VT>
@@ -637,29 +654,82 @@ static bool attention_bwd_vec(int heads, int k, int dcols, const void *Q, int ld
     return vec;
 }
 
-template <typename VT, bool COL>
-static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, AttBwdArgs<VT> A, const int groups, const bool vec,
+// one side's launch on the pattern (g, d) it walks; A: the call's fields and this side's outputs; map: null on the row side
+template <bool COL, typename VT, typename ARGS>
+static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, ARGS A, const uint32_t *map, const AttBwdCall &c,
                                      hipStream_t s)
 {
     if (g.m <= 0 || A.heads <= 0)
         return hipSuccess;
-    attention_bwd_fill<VT>(A, g, d, groups);
+    attention_bwd_fill<VT>(A, g, d, c.groups);
+    if constexpr (ARGS::BIASED)
+        att_set_bias(A.bias, d, map, c);
+    const bool vec = attention_bwd_vec<VT>(c.heads, c.k, c.d, c.Q, c.ldq, c.K, c.ldk, c.V, c.ldv, c.dO, c.lddo);
     const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 block(AT_BLOCK);
     if (A.heads == 1) {
         const dim3 grid(blocks);
         if (vec)
-            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, false>), grid, block, 0, s, A);
+            attention_bwd_enqueue<true, COL, false>(A, grid, s);
         else
-            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, false>), grid, block, 0, s, A);
+            attention_bwd_enqueue<false, COL, false>(A, grid, s);
     } else {
         const dim3 grid(blocks, (unsigned)((A.heads + A.hper - 1) / A.hper));
         if (vec)
-            hipLaunchKernelGGL((k_attention_bwd<VT, true, COL, true>), grid, block, 0, s, A);
+            attention_bwd_enqueue<true, COL, true>(A, grid, s);
         else
-            hipLaunchKernelGGL((k_attention_bwd<VT, false, COL, true>), grid, block, 0, s, A);
+            attention_bwd_enqueue<false, COL, true>(A, grid, s);
     }
     return hipGetLastError();
+}
+
+// The launcher of every backward unit: ARGS is the unit's argument struct (AttBwd..Args<VT>), which decides the kernels
+// (attention_bwd_enqueue) and the bias fields (att_set_bias).  g / d: the parent's pattern (the row kernel); c.gt / c.dt (edge: and
+// c.map): the transposed companion's (the column kernel, only when dK or dV is wanted).  The row kernel runs when dQ or dS is wanted
+// or the column kernel needs the workspace; dS is the row side's alone.
+template <typename VT, typename ARGS>
+hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const AttBwdCall &c, hipStream_t s)
+{
+    ARGS A{};
+    A.k = c.k;
+    A.d = c.d;
+    A.heads = c.heads;
+    A.ws = 4 * c.heads;
+    A.Q = (const VT *)c.Q;
+    A.K = (const VT *)c.K;
+    A.V = (const VT *)c.V;
+    A.dO = (const VT *)c.dO;
+    A.ldq = c.ldq;
+    A.ldk = c.ldk;
+    A.ldv = c.ldv;
+    A.lddo = c.lddo;
+    A.lddq = c.lddq;
+    A.lddk = c.lddk;
+    A.lddv = c.lddv;
+    void *dS = nullptr;
+    if constexpr (ARGS::BIASED)
+        dS = c.dS;
+    const bool column = c.gt && c.dt && (!ARGS::EDGE || c.map) && (c.dK || c.dV);
+    hipError_t e = hipSuccess;
+    if (c.dQ || dS || column) {
+        ARGS R = A;
+        R.dQ = c.k > 0 ? (VT *)c.dQ : nullptr;
+        R.work = column ? (VT *)c.work : nullptr;
+        if constexpr (ARGS::BIASED) {
+            R.dS = (VT *)dS;
+            R.ldds = c.ldds;
+        }
+        if (R.dQ || R.work || dS)
+            e = attention_bwd_side<false, VT>(g, d, R, nullptr, c, s);
+    }
+    if (e == hipSuccess && column) {
+        ARGS C = A;
+        C.dK = c.k > 0 ? (VT *)c.dK : nullptr;
+        C.dV = c.d > 0 ? (VT *)c.dV : nullptr;
+        C.work = (VT *)c.work;
+        if (C.dK || C.dV)
+            e = attention_bwd_side<true, VT>(*c.gt, *c.dt, C, c.map, c, s);
+    }
+    return e;
 }
 
 } // namespace csr5

@@ -176,6 +176,33 @@ __device__ __forceinline__ float att_bias_score(const AttEdgeBiasLowp<ST> &E, co
     return fma_vt(qk, E.c, b);
 }
 
+// The variant-specific part of a launch, forward and backward alike: the bias fields from the call.  side: the arrays of the pattern
+// the kernel walks (the parent's, or the companion's in the column kernel); map: null where that pattern is the parent's, the
+// companion's source map in the column kernel.
+template <typename VT>
+static void att_set_bias(AttBias<VT> &b, const DeviceArrays &side, const uint32_t *, const AttCall &c)
+{
+    b.val = (const VT *)side.val;
+    b.slopes = (const VT *)c.slopes;
+    b.c = (VT)c.scale;
+}
+template <typename VT>
+static void att_set_bias(AttEdgeBias<VT> &b, const DeviceArrays &, const uint32_t *map, const AttCall &c)
+{
+    b.B = (const VT *)c.B;
+    b.map = map;
+    b.ldb = c.ldb;
+    b.c = (VT)c.scale;
+}
+template <typename ST>
+static void att_set_bias(AttEdgeBiasLowp<ST> &b, const DeviceArrays &, const uint32_t *, const AttCall &c)
+{
+    static_assert(sizeof(ST) == 2, "a 16-bit operand type");
+    b.B = (const ST *)c.B;
+    b.ldb = c.ldb;
+    b.c = (float)c.scale;
+}
+
 // What a kernel stores of a computed value x: x itself where the storage type is the compute type; otherwise x rounded ONCE, to
 // nearest even, by the cast.  The empty asm keeps x, a float, whole in a register first: without it the compiler folds the
 // multiplication that produced x into the conversion (v_fma_mixlo_f16), which rounds the exact product to fp16 and skips the float

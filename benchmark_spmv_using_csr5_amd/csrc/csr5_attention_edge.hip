@@ -28,52 +28,23 @@
 
 namespace csr5 {
 
-// groups: the head groups over grid.y, 0 for the rule (att_heads_per_group)
-template <typename VT>
-static hipError_t attention_edge_typed(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *B,
-                                       int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                                       void *O, int ldo, hipStream_t s)
-{
-    if (g.m <= 0 || dcols <= 0 || heads <= 0)
-        return hipSuccess;
-    AttEdgeArgs<VT> A;
-    attention_fill<VT>(A, g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo);
-    A.bias.B = (const VT *)B;
-    A.bias.map = nullptr;
-    A.bias.ldb = ldb;
-    A.bias.c = (VT)scale;
-    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 grid(blocks, (unsigned)((heads + A.hper - 1) / A.hper)), block(AT_BLOCK);
-    if (attention_vec<VT>(heads, Q, ldq, K, ldk, k))
-        hipLaunchKernelGGL((k_attention_edge<VT, true>), grid, block, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_attention_edge<VT, false>), grid, block, 0, s, A);
-    return hipGetLastError();
-}
-
-// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / -DCSR5_ATTENTION_ONLY_F32), as csr5_attention.hip.
-#define CSR5_EDGE_PARAMS                                                                                                                  \
-    const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *B, int ldb, const void *Q, int ldq,        \
-        const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s
-#define CSR5_EDGE_ARGS g, d, heads, groups, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s
+// The product build compiles this file once per value type (-DCSR5_ATTENTION_ONLY_F64 / _F32), as csr5_sddmm.hip:
+// each object holds the shared launcher's instantiation on its type, the fp64 one the dispatcher as well.
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_edge_f64(CSR5_EDGE_PARAMS) { return attention_edge_typed<double>(CSR5_EDGE_ARGS); }
+extern template AttLaunch attention_launch<AttEdgeArgs<float>>;
+template AttLaunch attention_launch<AttEdgeArgs<double>>;
 #endif
 #if !defined(CSR5_ATTENTION_ONLY_F64)
-hipError_t launch_mha_edge_f32(CSR5_EDGE_PARAMS) { return attention_edge_typed<float>(CSR5_EDGE_ARGS); }
+template AttLaunch attention_launch<AttEdgeArgs<float>>;
 #endif
 
 #if !defined(CSR5_ATTENTION_ONLY_F32)
-hipError_t launch_mha_edge_f32(CSR5_EDGE_PARAMS);
-
-hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale, const void *B,
-                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
-                           int ldo, hipStream_t s)
+hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s)
 {
-    return value_type == CSR5HIP_F64 ? launch_mha_edge_f64(CSR5_EDGE_ARGS) : launch_mha_edge_f32(CSR5_EDGE_ARGS);
+    if (value_type == CSR5HIP_F64)
+        return attention_launch<AttEdgeArgs<double>>(g, d, c, s);
+    return attention_launch<AttEdgeArgs<float>>(g, d, c, s);
 }
 #endif
-#undef CSR5_EDGE_PARAMS
-#undef CSR5_EDGE_ARGS
 
 } // namespace csr5

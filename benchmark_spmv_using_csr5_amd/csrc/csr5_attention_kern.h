@@ -394,17 +394,38 @@ __global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_LOWP_WAVES k_attention_lowp
     CSR5_ATTENTION_KERNEL_BODY(true)
 }
 
-// the pattern, the operands and the head groups of a launch.  groups: the head groups over grid.y, 0 for the rule.  VT: the type
-// the operands are stored in
+// the kernels of an argument struct, as overloads, so that the launcher below is written once.  MH: only the plain call has a
+// single-head instantiation; the others are always the packed call
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention<VT, VEC, MH>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttBiasArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_biased<VT, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttEdgeArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_edge<VT, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename ST>
+static void attention_enqueue(const AttLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_lowp<ST, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+
+// the pattern, the operands and the head groups of a launch.  VT: the type the operands are stored in
 template <typename VT, typename ARGS>
-static void attention_fill(ARGS &A, const Geometry &g, const DeviceArrays &d, int heads, int groups, const void *Q, int ldq,
-                           const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo)
+static void attention_fill(ARGS &A, const Geometry &g, const DeviceArrays &d, const AttCall &c)
 {
     A.m = g.m;
-    A.k = k;
-    A.d = dcols;
-    A.heads = heads;
-    A.hper = groups > 0 ? (heads + groups - 1) / groups : att_heads_per_group(g.m, heads);
+    A.k = c.k;
+    A.d = c.d;
+    A.heads = c.heads;
+    A.hper = c.groups > 0 ? (c.heads + c.groups - 1) / c.groups : att_heads_per_group(g.m, c.heads);
     A.sigma = g.sigma > 0 ? g.sigma : 1;
     A.T = g.tile_elems > 0 ? g.tile_elems : OMEGA;
     A.tiles = g.p > 1 ? g.p - 1 : 0;
@@ -412,14 +433,14 @@ static void attention_fill(ARGS &A, const Geometry &g, const DeviceArrays &d, in
     A.row_ptr = d.row_ptr;
     A.col = d.col;
     A.tile_ptr = d.tile_ptr;
-    A.Q = (const VT *)Q;
-    A.K = (const VT *)K;
-    A.V = (const VT *)V;
-    A.O = (VT *)O;
-    A.ldq = ldq;
-    A.ldk = ldk;
-    A.ldv = ldv;
-    A.ldo = ldo;
+    A.Q = (const VT *)c.Q;
+    A.K = (const VT *)c.K;
+    A.V = (const VT *)c.V;
+    A.O = (VT *)c.O;
+    A.ldq = c.ldq;
+    A.ldk = c.ldk;
+    A.ldv = c.ldv;
+    A.ldo = c.ldo;
 }
 
 // 16-byte loads: at least one whole block, and every head's slice of every row of Q and of K starts on a 16-byte boundary
@@ -429,6 +450,36 @@ static bool attention_vec(int heads, const void *Q, int ldq, const void *K, int 
     return k >= 32 / (int)sizeof(VT) && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(K) % 16 == 0 &&
            ((size_t)ldq * sizeof(VT)) % 16 == 0 && ((size_t)ldk * sizeof(VT)) % 16 == 0 &&
            (heads == 1 || ((size_t)k * sizeof(VT)) % 16 == 0);
+}
+
+// The launcher of every forward unit: ARGS is the unit's argument struct, which decides the kernels (attention_enqueue) and the
+// bias fields (att_set_bias).  heads == 1 of the plain call is the single-head instantiation, on a grid without head groups.
+template <typename ARGS>
+hipError_t attention_launch(const Geometry &g, const DeviceArrays &d, const AttCall &c, hipStream_t s)
+{
+    using ST = typename ARGS::ST;
+    if (g.m <= 0 || c.d <= 0 || c.heads <= 0)
+        return hipSuccess;
+    ARGS A;
+    attention_fill<ST>(A, g, d, c);
+    if constexpr (ARGS::BIASED)
+        att_set_bias(A.bias, d, nullptr, c);
+    const bool vec = attention_vec<ST>(c.heads, c.Q, c.ldq, c.K, c.ldk, c.k);
+    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
+    if (c.heads == 1) {
+        const dim3 grid(blocks);
+        if (vec)
+            attention_enqueue<true, false>(A, grid, s);
+        else
+            attention_enqueue<false, false>(A, grid, s);
+    } else {
+        const dim3 grid(blocks, (unsigned)((c.heads + A.hper - 1) / A.hper));
+        if (vec)
+            attention_enqueue<true, true>(A, grid, s);
+        else
+            attention_enqueue<false, true>(A, grid, s);
+    }
+    return hipGetLastError();
 }
 
 } // namespace csr5

@@ -34,54 +34,24 @@
 
 namespace csr5 {
 
-// groups: the head groups over grid.y, 0 for the rule (att_heads_per_group)
-template <typename ST>
-static hipError_t attention_lowp_typed(const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *B,
-                                       int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                                       void *O, int ldo, hipStream_t s)
-{
-    static_assert(sizeof(ST) == 2, "a 16-bit operand type");
-    if (g.m <= 0 || dcols <= 0 || heads <= 0)
-        return hipSuccess;
-    AttLowpArgs<ST> A;
-    attention_fill<ST>(A, g, d, heads, groups, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo);
-    A.bias.B = (const ST *)B;
-    A.bias.ldb = ldb;
-    A.bias.c = (float)scale;
-    const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
-    const dim3 grid(blocks, (unsigned)((heads + A.hper - 1) / A.hper)), block(AT_BLOCK);
-    if (attention_vec<ST>(heads, Q, ldq, K, ldk, k))
-        hipLaunchKernelGGL((k_attention_lowp<ST, true>), grid, block, 0, s, A);
-    else
-        hipLaunchKernelGGL((k_attention_lowp<ST, false>), grid, block, 0, s, A);
-    return hipGetLastError();
-}
-
-// The product build compiles this file once per operand type (-DCSR5_LOWP_ONLY_BF16 / -DCSR5_LOWP_ONLY_F16), as the other units
-// are compiled per value type.
-#define CSR5_LOWP_PARAMS                                                                                                                  \
-    const Geometry &g, const DeviceArrays &d, int heads, int groups, double scale, const void *B, int ldb, const void *Q, int ldq,        \
-        const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s
-#define CSR5_LOWP_ARGS g, d, heads, groups, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, dcols, O, ldo, s
+// The product build compiles this file once per operand type (-DCSR5_LOWP_ONLY_BF16 / -DCSR5_LOWP_ONLY_F16), as the other units are
+// compiled per value type: each object holds the shared launcher's instantiation on its type, the bf16 one the dispatcher as well.
 #if !defined(CSR5_LOWP_ONLY_F16)
-hipError_t launch_mha_lowp_bf16(CSR5_LOWP_PARAMS) { return attention_lowp_typed<__bf16>(CSR5_LOWP_ARGS); }
+extern template AttLaunch attention_launch<AttLowpArgs<_Float16>>;
+template AttLaunch attention_launch<AttLowpArgs<__bf16>>;
 #endif
 #if !defined(CSR5_LOWP_ONLY_BF16)
-hipError_t launch_mha_lowp_f16(CSR5_LOWP_PARAMS) { return attention_lowp_typed<_Float16>(CSR5_LOWP_ARGS); }
+template AttLaunch attention_launch<AttLowpArgs<_Float16>>;
 #endif
 
 #if !defined(CSR5_LOWP_ONLY_F16)
-hipError_t launch_mha_lowp_f16(CSR5_LOWP_PARAMS);
-
 // operand_type: CSR5HIP_BF16 or CSR5HIP_F16 (the caller has checked it)
-hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, int heads, int groups, double scale, const void *B,
-                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
-                           int ldo, hipStream_t s)
+hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, const AttCall &c, hipStream_t s)
 {
-    return operand_type == CSR5HIP_BF16 ? launch_mha_lowp_bf16(CSR5_LOWP_ARGS) : launch_mha_lowp_f16(CSR5_LOWP_ARGS);
+    if (operand_type == CSR5HIP_BF16)
+        return attention_launch<AttLowpArgs<__bf16>>(g, d, c, s);
+    return attention_launch<AttLowpArgs<_Float16>>(g, d, c, s);
 }
 #endif
-#undef CSR5_LOWP_PARAMS
-#undef CSR5_LOWP_ARGS
 
 } // namespace csr5

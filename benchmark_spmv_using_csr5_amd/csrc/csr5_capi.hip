@@ -1710,296 +1710,187 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
     return CSR5HIP_SUCCESS;
 }
 
-// O = softmax over every row's stored entries of (Q K^T) times V, in one launch (csr5_attention.hip).  Reads row_ptr, tile_ptr and the
-// tile-ordered column_index of the parent, whatever path spmv() takes; allocates nothing, changes nothing: enqueue-only.
-int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
-                      void *d_O, int ldo)
+// ---- attention on the pattern (csr5_attention*.hip) ---------------------------------------------------------------------------
+// The nine entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
+// trivial cases, the launch.  The single-head calls are heads = 1.  The forward reads row_ptr, tile_ptr and the tile-ordered
+// column_index of the parent, whatever path spmv() takes (biased: its tile-ordered values too); it allocates nothing and changes
+// nothing: enqueue-only.  lowp: the call names the type its operands are stored in (operand_type, judged here); the others take the handle's.
+static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, int operand_type, const AttCall &c)
 {
-    if (!h || k < 0 || d < 0 || ldq < k || ldk < k || ldv < d || ldo < d)
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
+        return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
+    if (c.ldq < wk || c.ldk < wk || c.ldv < wd || c.ldo < wd || (c.B && c.ldb < c.heads))
         return CSR5HIP_INVALID_ARGUMENT;
     const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
+    if (c.heads > 0 && nnz > 0 && ((c.k > 0 && (!c.Q || !c.K)) || (c.d > 0 && !c.V)))
         return CSR5HIP_INVALID_ARGUMENT;
-    if (d > 0 && h->g.m > 0 && !d_O)
+    if (c.heads > 0 && c.d > 0 && h->g.m > 0 && !c.O)
         return CSR5HIP_INVALID_ARGUMENT;
     if (h->format == CSR5HIP_FORMAT_CSR)
         return CSR5HIP_UNSUPPORTED_CSR_SPMV;
     if (h->format != CSR5HIP_FORMAT_CSR5)
         return CSR5HIP_UNKOWN_FORMAT;
-    if (d == 0 || h->g.m <= 0)
+    if (c.heads == 0 || c.d == 0 || h->g.m <= 0)
         return CSR5HIP_SUCCESS;
-    HIP_TRY(launch_attention(h->g, h->d, h->value_type, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo, h->stream));
+    if (lowp)
+        HIP_TRY(launch_mha_lowp(h->g, h->d, operand_type, c, h->stream));
+    else if (variant == ATT_PLAIN)
+        HIP_TRY(launch_mha(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_BIASED)
+        HIP_TRY(launch_mha_biased(h->g, h->d, h->value_type, c, h->stream));
+    else
+        HIP_TRY(launch_mha_edge(h->g, h->d, h->value_type, c, h->stream));
     return CSR5HIP_SUCCESS;
 }
 
-// dQ, dK, dV of csr5hip_attention in two launches (csr5_attention_bwd.hip): the row kernel on the parent's pattern, the column kernel on
-// the transposed companion's.  Allocates nothing, changes nothing of the handle or of its companion: enqueue-only.
+// The backward in two launches: the row kernel on the parent's pattern (it writes dQ, and dS / dB when given), the column kernel on
+// the transposed companion's (dK, dV; edge: it finds an entry's rank through the companion's source map, b_at_map, passed, not
+// copied).  Allocates nothing, changes nothing of the handle or of its companion: enqueue-only.  c: everything but gt, dt and map,
+// which come from the handle.
+static int attention_backward(csr5hip_handle h, const char *name, AttVariant variant, AttBwdCall c)
+{
+    if (!h || c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
+    if (c.ldq < wk || c.ldk < wk || c.lddq < wk || c.lddk < wk || c.ldv < wd || c.lddo < wd || c.lddv < wd ||
+        (c.B && c.ldb < c.heads) || (c.dS && c.ldds < c.heads))
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool column = c.dK || c.dV; // the column side: needs the workspace and the companion
+    const bool any = c.dQ || column || c.dS;
+    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
+    if (c.heads > 0 && any && nnz > 0 && ((c.k > 0 && (!c.Q || !c.K)) || (c.d > 0 && (!c.V || !c.dO)) || (column && !c.work)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (column && !h->at_built) {
+        g_last_error = std::string(name) + ": dK and dV need the transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (!any || c.heads == 0)
+        return CSR5HIP_SUCCESS;
+    const size_t vs = h->vsize();
+    // no entries (and then no companion arrays, and no element of dS / dB): the zeros
+    if (nnz == 0 || (column && (!h->at || (variant == ATT_EDGE && !h->b_at_map.ptr)))) {
+        if (c.dQ && c.k > 0 && h->g.m > 0)
+            HIP_TRY(hipMemset2DAsync(c.dQ, (size_t)c.lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
+        if (c.dK && c.k > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(c.dK, (size_t)c.lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
+        if (c.dV && c.d > 0 && h->g.n > 0)
+            HIP_TRY(hipMemset2DAsync(c.dV, (size_t)c.lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
+        return CSR5HIP_SUCCESS;
+    }
+    if (column) {
+        c.gt = &h->at->g;
+        c.dt = &h->at->d;
+        c.map = variant == ATT_EDGE ? (const uint32_t *)h->b_at_map.ptr : nullptr;
+    }
+    if (variant == ATT_PLAIN)
+        HIP_TRY(launch_mha_bwd(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_BIASED)
+        HIP_TRY(launch_mha_biased_bwd(h->g, h->d, h->value_type, c, h->stream));
+    else
+        HIP_TRY(launch_mha_edge_bwd(h->g, h->d, h->value_type, c, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
+// the descriptors of the entry points' arguments; what a call does not have stays null / 0, the scale 1 (finite)
+static AttCall att_call(int heads, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int d, void *O, int ldo)
+{
+    AttCall c{};
+    c.heads = heads; c.k = k; c.d = d; c.scale = 1.0;
+    c.Q = Q; c.ldq = ldq; c.K = K; c.ldk = ldk; c.V = V; c.ldv = ldv; c.O = O; c.ldo = ldo;
+    return c;
+}
+static AttBwdCall att_bwd_call(int heads, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int d,
+                               const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work)
+{
+    AttBwdCall c{};
+    static_cast<AttCall &>(c) = att_call(heads, Q, ldq, K, ldk, k, V, ldv, d, nullptr, 0);
+    c.dO = dO; c.lddo = lddo; c.dQ = dQ; c.lddq = lddq; c.dK = dK; c.lddk = lddk; c.dV = dV; c.lddv = lddv; c.work = work;
+    return c;
+}
+
+int csr5hip_attention(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
+                      void *d_O, int ldo)
+{
+    return attention_forward(h, ATT_PLAIN, false, 0, att_call(1, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo));
+}
+
 int csr5hip_attention_backward(csr5hip_handle h, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv,
                                int d, const void *d_dO, int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv,
                                void *d_work)
 {
-    if (!h || k < 0 || d < 0 || ldq < k || ldk < k || lddq < k || lddk < k || ldv < d || lddo < d || lddv < d)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
-    const bool any = d_dQ || column;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (column && !h->at_built) {
-        g_last_error = "csr5hip_attention_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
-        return CSR5HIP_INVALID_ARGUMENT;
-    }
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (!any)
-        return CSR5HIP_SUCCESS;
-    const size_t vs = h->vsize();
-    if (nnz == 0 || (column && !h->at)) { // no entries (and then no companion arrays): the zeros
-        if (d_dQ && k > 0 && h->g.m > 0)
-            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)k * vs, (size_t)h->g.m, h->stream));
-        if (d_dK && k > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)k * vs, (size_t)h->g.n, h->stream));
-        if (d_dV && d > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)d * vs, (size_t)h->g.n, h->stream));
-        return CSR5HIP_SUCCESS;
-    }
-    HIP_TRY(launch_attention_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr, h->value_type, d_Q, ldq, d_K, ldk,
-                                 k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work, h->stream));
-    return CSR5HIP_SUCCESS;
+    const AttBwdCall c = att_bwd_call(1, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    return attention_backward(h, "csr5hip_attention_backward", ATT_PLAIN, c);
 }
 
-// csr5hip_attention for `heads` heads on packed operands in one launch (csr5_attention.hip, the head loop inside the row classes)
+// `heads` heads on packed operands in one launch (the head loop inside the row classes)
 int csr5hip_mha(csr5hip_handle h, int heads, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
                 void *d_O, int ldo)
 {
-    if (!h || heads < 0 || k < 0 || d < 0)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (heads == 0 || d == 0 || h->g.m <= 0)
-        return CSR5HIP_SUCCESS;
-    HIP_TRY(launch_mha(h->g, h->d, h->value_type, heads, 0, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo, h->stream));
-    return CSR5HIP_SUCCESS;
+    return attention_forward(h, ATT_PLAIN, false, 0, att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo));
 }
 
-// csr5hip_attention_backward for `heads` heads on packed operands in two launches (csr5_attention_bwd.hip)
 int csr5hip_mha_backward(csr5hip_handle h, int heads, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv,
                          int d, const void *d_dO, int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv,
                          void *d_work)
 {
-    if (!h || heads < 0 || k < 0 || d < 0)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || lddq < wk || lddk < wk || ldv < wd || lddo < wd || lddv < wd)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
-    const bool any = d_dQ || column;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (column && !h->at_built) {
-        g_last_error = "csr5hip_mha_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
-        return CSR5HIP_INVALID_ARGUMENT;
-    }
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (!any || heads == 0)
-        return CSR5HIP_SUCCESS;
-    const size_t vs = h->vsize();
-    if (nnz == 0 || (column && !h->at)) { // no entries (and then no companion arrays): the zeros
-        if (d_dQ && k > 0 && h->g.m > 0)
-            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
-        if (d_dK && k > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
-        if (d_dV && d > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
-        return CSR5HIP_SUCCESS;
-    }
-    HIP_TRY(launch_mha_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr, h->value_type, heads, 0, d_Q, ldq, d_K,
-                           ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work, h->stream));
-    return CSR5HIP_SUCCESS;
+    const AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    return attention_backward(h, "csr5hip_mha_backward", ATT_PLAIN, c);
 }
 
-// csr5hip_mha with the score fma(qk, scale, slopes[h] * value of the entry) in one launch (csr5_attention_bias.hip): reads the
-// parent's tile-ordered values next to its columns and writes nothing of the handle; allocates nothing: enqueue-only.
+// the score fma(qk, scale, slopes[h] * value of the entry): reads the parent's tile-ordered values next to its columns (the column
+// kernel of the backward: the companion's)
 int csr5hip_mha_biased(csr5hip_handle h, int heads, double scale, const void *d_slopes, const void *d_Q, int ldq, const void *d_K, int ldk,
                        int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
 {
-    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd)
-        return CSR5HIP_INVALID_ARGUMENT;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (heads == 0 || d == 0 || h->g.m <= 0)
-        return CSR5HIP_SUCCESS;
-    HIP_TRY(launch_mha_biased(h->g, h->d, h->value_type, heads, 0, scale, d_slopes, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo,
-                              h->stream));
-    return CSR5HIP_SUCCESS;
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.slopes = d_slopes;
+    return attention_forward(h, ATT_BIASED, false, 0, c);
 }
 
-// csr5hip_mha_backward for those scores in two launches (csr5_attention_bwd_bias.hip): the row kernel reads the parent's values and
-// writes d_dS when it is given, the column kernel reads the transposed companion's.  Allocates nothing, changes nothing of the
-// handle or of its companion: enqueue-only.
 int csr5hip_mha_biased_backward(csr5hip_handle h, int heads, double scale, const void *d_slopes, const void *d_Q, int ldq, const void *d_K,
                                 int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo, void *d_dQ, int lddq,
                                 void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dS, int ldds)
 {
-    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || lddq < wk || lddk < wk || ldv < wd || lddo < wd || lddv < wd || (d_dS && ldds < heads))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
-    const bool any = d_dQ || column || d_dS;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (column && !h->at_built) {
-        g_last_error = "csr5hip_mha_biased_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
-        return CSR5HIP_INVALID_ARGUMENT;
-    }
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (!any || heads == 0)
-        return CSR5HIP_SUCCESS;
-    const size_t vs = h->vsize();
-    if (nnz == 0 || (column && !h->at)) { // no entries (and then no companion arrays, and no element of dS): the zeros
-        if (d_dQ && k > 0 && h->g.m > 0)
-            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
-        if (d_dK && k > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
-        if (d_dV && d > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
-        return CSR5HIP_SUCCESS;
-    }
-    HIP_TRY(launch_mha_biased_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr, h->value_type, heads, 0, scale,
-                                  d_slopes, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work,
-                                  d_dS, ldds, h->stream));
-    return CSR5HIP_SUCCESS;
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.slopes = d_slopes; c.dS = d_dS; c.ldds = ldds;
+    return attention_backward(h, "csr5hip_mha_biased_backward", ATT_BIASED, c);
 }
 
-// csr5hip_mha with the score fma(qk, scale, B[e * ldb + h]), B a caller's tensor in CSR order, in one launch
-// (csr5_attention_edge.hip): reads the parent's pattern and nothing of its values; allocates nothing: enqueue-only.
+// the score fma(qk, scale, B[e * ldb + h]), B a caller's tensor in CSR order: reads the parent's pattern and nothing of its values
 int csr5hip_mha_edge_bias(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq, const void *d_K,
                           int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
 {
-    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd || (d_B && (long long)ldb < (long long)heads))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (heads == 0 || d == 0 || h->g.m <= 0)
-        return CSR5HIP_SUCCESS;
-    HIP_TRY(launch_mha_edge(h->g, h->d, h->value_type, heads, 0, scale, d_B, ldb, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo,
-                            h->stream));
-    return CSR5HIP_SUCCESS;
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb;
+    return attention_forward(h, ATT_EDGE, false, 0, c);
 }
 
-// csr5hip_mha_edge_bias on operands stored in bf16 / fp16, computed in float (csr5_attention_lowp.hip): reads the parent's pattern and
-// nothing of its values, so the handle's value type plays no part; allocates nothing: enqueue-only.
+// csr5hip_mha_edge_bias on operands stored in bf16 / fp16, computed in float (csr5_attention_lowp.hip): the handle's value type plays
+// no part
 int csr5hip_mha_lowp(csr5hip_handle h, int operand_type, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq,
                      const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
 {
-    if (!h)
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
-        return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
-    if (heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || ldv < wd || ldo < wd || (d_B && (long long)ldb < (long long)heads))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && !d_V)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (heads > 0 && d > 0 && h->g.m > 0 && !d_O)
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (heads == 0 || d == 0 || h->g.m <= 0)
-        return CSR5HIP_SUCCESS;
-    HIP_TRY(launch_mha_lowp(h->g, h->d, operand_type, heads, 0, scale, d_B, ldb, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo, h->stream));
-    return CSR5HIP_SUCCESS;
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb;
+    return attention_forward(h, ATT_EDGE, true, operand_type, c);
 }
 
-// csr5hip_mha_backward for those scores in two launches (csr5_attention_bwd_edge.hip): the row kernel reads B at the entry's CSR rank
-// and writes d_dB when it is given, the column kernel finds the rank through the companion's source map (b_at_map, passed, not
-// copied).  Reads nothing of the values, allocates nothing, changes nothing of the handle or of its companion: enqueue-only.
 int csr5hip_mha_edge_bias_backward(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq,
                                    const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo,
                                    void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dB, int lddb)
 {
-    if (!h || heads < 0 || k < 0 || d < 0 || !std::isfinite(scale))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const long long wk = (long long)heads * k, wd = (long long)heads * d;
-    if (ldq < wk || ldk < wk || lddq < wk || lddk < wk || ldv < wd || lddo < wd || lddv < wd ||
-        (d_B && (long long)ldb < (long long)heads) || (d_dB && (long long)lddb < (long long)heads))
-        return CSR5HIP_INVALID_ARGUMENT;
-    const bool column = d_dK || d_dV; // the column side: needs the workspace and the companion
-    const bool any = d_dQ || column || d_dB;
-    const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
-    if (heads > 0 && any && nnz > 0 && ((k > 0 && (!d_Q || !d_K)) || (d > 0 && (!d_V || !d_dO)) || (column && !d_work)))
-        return CSR5HIP_INVALID_ARGUMENT;
-    if (column && !h->at_built) {
-        g_last_error = "csr5hip_mha_edge_bias_backward: dK and dV need the transposed companion, call csr5hip_build_transpose first";
-        return CSR5HIP_INVALID_ARGUMENT;
-    }
-    if (h->format == CSR5HIP_FORMAT_CSR)
-        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
-    if (h->format != CSR5HIP_FORMAT_CSR5)
-        return CSR5HIP_UNKOWN_FORMAT;
-    if (!any || heads == 0)
-        return CSR5HIP_SUCCESS;
-    const size_t vs = h->vsize();
-    if (nnz == 0 || (column && (!h->at || !h->b_at_map.ptr))) { // no entries (and then no companion arrays, no element of dB): the zeros
-        if (d_dQ && k > 0 && h->g.m > 0)
-            HIP_TRY(hipMemset2DAsync(d_dQ, (size_t)lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
-        if (d_dK && k > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dK, (size_t)lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
-        if (d_dV && d > 0 && h->g.n > 0)
-            HIP_TRY(hipMemset2DAsync(d_dV, (size_t)lddv * vs, 0, (size_t)wd * vs, (size_t)h->g.n, h->stream));
-        return CSR5HIP_SUCCESS;
-    }
-    HIP_TRY(launch_mha_edge_bwd(h->g, h->d, column ? &h->at->g : nullptr, column ? &h->at->d : nullptr,
-                                column ? (const uint32_t *)h->b_at_map.ptr : nullptr, h->value_type, heads, 0, scale, d_B, ldb, d_Q, ldq,
-                                d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work, d_dB, lddb, h->stream));
-    return CSR5HIP_SUCCESS;
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
+    return attention_backward(h, "csr5hip_mha_edge_bias_backward", ATT_EDGE, c);
 }
 
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------

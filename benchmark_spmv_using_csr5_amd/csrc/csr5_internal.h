@@ -247,52 +247,66 @@ hipError_t launch_sddmm(const Geometry &g, const DeviceArrays &d, int value_type
 hipError_t launch_row_softmax(int m, const int32_t *row_ptr, int value_type, const void *scores, void *out, hipStream_t s);
 hipError_t launch_row_softmax_grad(int m, const int32_t *row_ptr, int value_type, const void *p, const void *g, void *out,
                                    hipStream_t s);
-// csr5_attention.hip: O = softmax_row(Q K^T on the pattern) V in one pass, nothing of length nnz written; reads row_ptr, tile_ptr and
-// the tile-ordered column_index (g, d: CSR5 form) and writes EVERY row of O in columns 0 .. dcols-1; no workspace
-hipError_t launch_attention(const Geometry &g, const DeviceArrays &d, int value_type, const void *Q, int ldq, const void *K, int ldk,
-                            int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
-// the same for `heads` heads on packed operands (head h in columns h k .. / h dcols ..) in one launch; groups: the head groups over
-// grid.y, 0 for the rule, a function of (m, heads).  heads = 1 is launch_attention
-hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, const void *Q, int ldq,
-                      const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O, int ldo, hipStream_t s);
-// csr5_attention_bwd.hip: the gradients of launch_attention's O for Q, K and V.  The row kernel walks the parent's pattern (g, d) and
-// writes dQ and the workspace (4 values per row); the column kernel walks the transposed companion's (gt, dt; null when neither dK
-// nor dV is wanted) and writes dK and dV.  A null output is not wanted; EVERY row of a wanted one is written in its k / dcols columns
-hipError_t launch_attention_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
-                                const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO,
-                                int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
-// the same for `heads` heads on packed operands; the workspace holds 4 values per (row, head), a row's heads adjacent
-hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type, int heads,
-                          int groups, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                          const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV, int lddv, void *work, hipStream_t s);
-// csr5_attention_bias.hip: launch_mha with the score s = fma(qk, (VT)scale, slopes[h] * a_e), a_e the value of the entry in d.val
-// (tile order: the position of its column); slopes: `heads` device values, or null (no multiplication).  d.val is only read
-hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale,
-                             const void *slopes, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols,
-                             void *O, int ldo, hipStream_t s);
-// csr5_attention_bwd_bias.hip: launch_mha_bwd for those scores; dQ and dK take ds * (VT)scale.  The row kernel reads d.val, the
-// column kernel dt->val; dS (null: not wanted): ds of entry e (CSR rank) and head h at dS[e * ldds + h], written by the row kernel
-hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, int value_type,
-                                 int heads, int groups, double scale, const void *slopes, const void *Q, int ldq, const void *K, int ldk,
-                                 int k, const void *V, int ldv, int dcols, const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk,
-                                 void *dV, int lddv, void *work, void *dS, int ldds, hipStream_t s);
-// csr5_attention_edge.hip: launch_mha with the score s = fma(qk, (VT)scale, B[e * ldb + h]), e the entry's CSR rank; B: a caller's
-// nnz x heads device values, or null (b = +0, nothing read).  d.val is NOT read
-hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, int heads, int groups, double scale, const void *B,
-                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
-                           int ldo, hipStream_t s);
+// ---- attention on the pattern (csr5_attention*.hip) ----
+// One call of the forward, whatever the variant: `heads` heads on packed operands (head h in columns h k .. of Q and K, h d .. of V
+// and O; heads = 1 is the single-head call).  groups: the head groups over grid.y, 0 for the rule, a function of (m, heads).  The
+// variant's launcher reads the bias fields that belong to it and no others.
+struct AttCall {
+    int heads, groups, k, d;
+    const void *Q;
+    int ldq;
+    const void *K;
+    int ldk;
+    const void *V;
+    int ldv;
+    void *O;
+    int ldo;
+    double scale;       // biased and edge: s = fma(qk, (VT)scale, b)
+    const void *slopes; // biased: b = slopes[h] * a_e, a_e the entry's value in d.val; `heads` device values, or null (b = a_e)
+    const void *B;      // edge: b = B[e * ldb + h], e the entry's CSR rank; a caller's nnz x heads device values, or null (b = +0)
+    int ldb;
+};
+// One call of the backward: the forward's operands, the gradient of O, the wanted outputs (null: not wanted; EVERY row of a wanted
+// one is written in its heads k / heads d columns) and the transposed companion the column kernel walks (gt, dt; edge: and its source
+// map, position in A^T's CSR -> position in A's; all null when neither dK nor dV is wanted).  work: 4 values per (row, head), a row's
+// heads adjacent.  dS (biased; the edge call's dB): ds of entry e (CSR rank) and head h at dS[e * ldds + h], written by the row kernel.
+struct AttBwdCall : AttCall {
+    const void *dO;
+    int lddo;
+    void *dQ;
+    int lddq;
+    void *dK;
+    int lddk;
+    void *dV;
+    int lddv;
+    void *work;
+    void *dS;
+    int ldds;
+    const Geometry *gt;
+    const DeviceArrays *dt;
+    const uint32_t *map;
+};
+enum AttVariant { ATT_PLAIN, ATT_BIASED, ATT_EDGE };
+// the type of the launcher templates' instantiations (attention_launch, attention_bwd_launch), one per unit and operand type
+using AttLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttCall &, hipStream_t);
+using AttBwdLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttBwdCall &, hipStream_t);
+// The forward, O = softmax_row(scores on the pattern) V in one pass, nothing of length nnz written; reads row_ptr, tile_ptr and the
+// tile-ordered column_index (g, d: CSR5 form) and writes EVERY row of O; no workspace.  One launcher per translation unit, each
+// csr5_attention_kern.h's attention_launch on its own argument struct.  value_type: CSR5HIP_F64 or CSR5HIP_F32
+// csr5_attention.hip (plain), csr5_attention_bias.hip (reads d.val), csr5_attention_edge.hip (d.val is NOT read):
+hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
+hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
+hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
 // csr5_attention_lowp.hip: launch_mha_edge on operands stored in 16 bits (operand_type: CSR5HIP_BF16 or CSR5HIP_F16, checked by the
 // caller; B, Q, K, V, O all of that type, leading dimensions in its elements), float arithmetic, O rounded once.  d.val is NOT read
-hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, int heads, int groups, double scale, const void *B,
-                           int ldb, const void *Q, int ldq, const void *K, int ldk, int k, const void *V, int ldv, int dcols, void *O,
-                           int ldo, hipStream_t s);
-// csr5_attention_bwd_edge.hip: launch_mha_bwd for those scores; dQ and dK take ds * (VT)scale.  map: the companion's source map
-// (position in A^T's CSR -> position in A's), by which the column kernel finds an entry's row of B; dB (null: not wanted): ds of
-// entry e and head h at dB[e * lddb + h], written by the row kernel.  Neither d.val nor dt->val is read
-hipError_t launch_mha_edge_bwd(const Geometry &g, const DeviceArrays &d, const Geometry *gt, const DeviceArrays *dt, const uint32_t *map,
-                               int value_type, int heads, int groups, double scale, const void *B, int ldb, const void *Q, int ldq,
-                               const void *K, int ldk, int k, const void *V, int ldv, int dcols, const void *dO, int lddo, void *dQ,
-                               int lddq, void *dK, int lddk, void *dV, int lddv, void *work, void *dB, int lddb, hipStream_t s);
+hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, const AttCall &c, hipStream_t s);
+// The backward in two launches, each csr5_attention_bwd_kern.h's attention_bwd_launch: the row kernel walks the parent's pattern (g, d)
+// and writes dQ, dS and the workspace, the column kernel the companion's and writes dK and dV; dQ and dK take ds * (VT)scale.  Biased:
+// the row kernel reads d.val, the column kernel c.dt->val.  Edge: neither is read
+// csr5_attention_bwd.hip, csr5_attention_bwd_bias.hip, csr5_attention_bwd_edge.hip:
+hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+hipError_t launch_mha_edge_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

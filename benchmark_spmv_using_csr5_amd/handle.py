@@ -214,63 +214,13 @@ class anonymouslibHandle:
         return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
 
     # -- attention on the pattern in one pass (csr5hip.h csr5hip_attention) -------------------------
-    def attention(self, Q, K, V, O) -> int:
-        """O = softmax over every row's stored entries of (Q K^T) times V in ONE launch: row i attends to the columns it stores.
-        Q (m, k), K (n, k), V (n, d) and O (m, d) as ``sddmm``'s operands (stride(1) == 1, leading dimension stride(0), so column
-        slices of wider tensors are legal: one call per head needs no copy); O shares storage with none of the inputs, which may
-        share among themselves.  EVERY row of O is written in columns 0 .. d-1 -- rows without entries with +0 -- so O may be
-        ``torch.empty``.  Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything
-        else raises ValueError before the library is called."""
+    def _attention_args(self, who: str, ins, outs, work):
+        """the checks of ``sddmm``'s operands for ``attention``'s 2-D tensors (rows, width), shaped like ``_mha_args``: ValueError,
+        naming the operand, unless each has the handle's dtype, its row count, stride(1) == 1 and rows that do not overlap; the
+        widths agree; ``work`` (wanted with dK or dV) holds 4 m values; no output shares storage with an input, another output
+        or ``work``; all live on one GPU (the device comes last).  Returns (k, d)."""
         dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        named = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("O", O, self._m, "d"))
-        for name, t, rows, width in named:  # (the checks of sddmm's operands; the device comes last)
-            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
-                raise ValueError(f"attention: {name} must be a torch tensor")
-            if str(t.dtype) != dt:
-                raise ValueError(f"attention: {name} has dtype {t.dtype}, the handle holds {dt}")
-            if t.dim() != 2 or t.shape[0] != rows:
-                raise ValueError(f"attention: {name} must have shape ({rows}, {width}), not {tuple(t.shape)}")
-            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError(f"attention: {name} must be row-major with stride(1) == 1, not {t.stride()}")
-            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
-                raise ValueError(f"attention: {name} rows overlap (stride(0) {t.stride(0)} < {width} = {t.shape[1]})")
-        if Q.shape[1] != K.shape[1]:
-            raise ValueError(f"attention: Q has {Q.shape[1]} columns, K {K.shape[1]}")
-        if V.shape[1] != O.shape[1]:
-            raise ValueError(f"attention: V has {V.shape[1]} columns, O {O.shape[1]}")
-        if self._nnz is None:
-            raise ValueError("attention: call inputCSR first")
-        k, d = int(Q.shape[1]), int(V.shape[1])
-        ld = [max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1]) for _, t, _, _ in named]
-        for name, t, _, _ in named[:3]:
-            if O.numel() and t.numel() and O.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                raise ValueError(f"attention: O shares storage with {name} (aliased)")
-        for name, t, _, _ in named:
-            if t.device.type != "cuda":
-                raise ValueError(f"attention: {name} must live on the GPU, not {t.device}")
-        if not (Q.device == K.device == V.device == O.device):
-            raise ValueError(f"attention: Q on {Q.device}, K on {K.device}, V on {V.device}, O on {O.device}")
-        return self.attention_ptr(Q, ld[0], K, ld[1], k, V, ld[2], d, O, ld[3])
-
-    def attention_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
-        """csr5hip_attention on raw device pointers (or tensors): Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
-        return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
-                                           _ptr(O), int(ldo))
-
-    # -- the gradients of attention in two launches (csr5hip.h csr5hip_attention_backward) -----------
-    def attentionBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
-        """The gradients of ``attention``'s O for Q, K and V from the gradient dO (m, d) arriving for O: dQ (m, k), dK (n, k) and
-        dV (n, d), each written in EVERY row (rows and columns of the matrix without entries with +0, so they may be
-        ``torch.empty``) or None when not wanted.  Operands as ``attention``'s (stride(1) == 1, leading dimension stride(0)); an
-        output shares storage with no input, no other output and not with ``work``.  dK and dV need ``work``, a contiguous 1-D
-        tensor of at least 4 m values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
-        Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything else raises ValueError
-        before the library is called."""
-        who = "attentionBackward"
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        for name, t, rows, width in ins + outs:  # (the checks of attention's operands; the device comes last)
+        for name, t, rows, width in ins + outs:
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"{who}: {name} must be a torch tensor")
             if str(t.dtype) != dt:
@@ -281,14 +231,14 @@ class anonymouslibHandle:
                 raise ValueError(f"{who}: {name} must be row-major with stride(1) == 1, not {t.stride()}")
             if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
                 raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < {width} = {t.shape[1]})")
+        Q, V = ins[0][1], ins[2][1]
         k, d = int(Q.shape[1]), int(V.shape[1])
         for name, t, _, width in ins[1:] + outs:
             want = k if width == "k" else d
             if t.shape[1] != want:
                 first = "Q" if width == "k" else "V"
                 raise ValueError(f"{who}: {first} has {want} columns, {name} {t.shape[1]}")
-        column = dK is not None or dV is not None
-        if work is not None or column:
+        if work is not None or any(name in ("dK", "dV") for name, _, _, _ in outs):
             if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
                 raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
             if str(work.dtype) != dt:
@@ -309,9 +259,42 @@ class anonymouslibHandle:
                 raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
         if any(t.device != Q.device for _, t, _, _ in ins + outs + scratch):
             raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t, _, _ in ins + outs + scratch))
+        return k, d
 
-        def ld(t):
-            return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+    @staticmethod
+    def _attention_ld(t) -> int:
+        return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+    def attention(self, Q, K, V, O) -> int:
+        """O = softmax over every row's stored entries of (Q K^T) times V in ONE launch: row i attends to the columns it stores.
+        Q (m, k), K (n, k), V (n, d) and O (m, d) as ``sddmm``'s operands (stride(1) == 1, leading dimension stride(0), so column
+        slices of wider tensors are legal: one call per head needs no copy); O shares storage with none of the inputs, which may
+        share among themselves.  EVERY row of O is written in columns 0 .. d-1 -- rows without entries with +0 -- so O may be
+        ``torch.empty``.  Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything
+        else raises ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        k, d = self._attention_args("attention", ins, (("O", O, self._m, "d"),), None)
+        ld = self._attention_ld
+        return self.attention_ptr(Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def attention_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
+        """csr5hip_attention on raw device pointers (or tensors): Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
+        return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                           _ptr(O), int(ldo))
+
+    # -- the gradients of attention in two launches (csr5hip.h csr5hip_attention_backward) -----------
+    def attentionBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
+        """The gradients of ``attention``'s O for Q, K and V from the gradient dO (m, d) arriving for O: dQ (m, k), dK (n, k) and
+        dV (n, d), each written in EVERY row (rows and columns of the matrix without entries with +0, so they may be
+        ``torch.empty``) or None when not wanted.  Operands as ``attention``'s (stride(1) == 1, leading dimension stride(0)); an
+        output shares storage with no input, no other output and not with ``work``.  dK and dV need ``work``, a contiguous 1-D
+        tensor of at least 4 m values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
+        Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything else raises ValueError
+        before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        k, d = self._attention_args("attentionBackward", ins, outs, work)
+        ld = self._attention_ld
         return self.attention_backward_ptr(Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ, ld(dQ) if dQ is not None else k,
                                            dK, ld(dK) if dK is not None else k, dV, ld(dV) if dV is not None else d, work)
 
@@ -423,6 +406,27 @@ class anonymouslibHandle:
         """the head count Q announces (judged by ``_mha_args`` afterwards); 0 when Q is no 3-D tensor, which that check rejects"""
         return int(Q.shape[1]) if hasattr(Q, "dim") and hasattr(Q, "shape") and Q.dim() == 3 else 0
 
+    def _mha_entry_tensor(self, who: str, name: str, t, heads: int, dt: str, holds: str, others=()) -> int:
+        """the checks of one per-entry tensor (``dS``, ``B``, ``dB``): ValueError unless it is a 2-D tensor of shape (nnz, heads)
+        and dtype ``dt`` with stride(1) == 1 and non-overlapping rows that shares storage with none of ``others`` (its device
+        is the caller's to judge).  Returns its row stride; ``heads`` for None."""
+        if t is None:
+            return heads
+        if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+            raise ValueError(f"{who}: {name} must be a torch tensor or None")
+        if str(t.dtype) != dt:
+            raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
+        if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
+            raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
+        if t.numel() and heads > 1 and t.stride(1) != 1:
+            raise ValueError(f"{who}: {name} must have stride(1) == 1, not {t.stride()}")
+        if t.numel() and t.shape[0] > 1 and t.stride(0) < heads:
+            raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads = {heads})")
+        for oname, o in others:
+            if hasattr(o, "untyped_storage") and t.numel() and o.numel() and t.untyped_storage().data_ptr() == o.untyped_storage().data_ptr():
+                raise ValueError(f"{who}: {name} shares a storage with {oname} (views of one storage are rejected, disjoint or not)")
+        return max(int(t.stride(0)), heads) if t.shape[0] > 1 and heads else heads
+
     def _mha_bias_args(self, who: str, heads: int, scale, slopes, dS, others):
         """the checks of ``scale``, ``slopes`` and ``dS``, made before those of the operands: ValueError unless scale is a finite
         number, slopes (or None) a contiguous 1-D GPU tensor of ``heads`` values of the handle's dtype, dS (or None) an
@@ -445,24 +449,9 @@ class anonymouslibHandle:
                 raise ValueError(f"{who}: slopes must be contiguous, not stride {slopes.stride()}")
             if slopes.device.type != "cuda":
                 raise ValueError(f"{who}: slopes must live on the GPU, not {slopes.device}")
-        ldds = heads
-        if dS is not None:
-            if not hasattr(dS, "data_ptr") or not hasattr(dS, "stride"):
-                raise ValueError(f"{who}: dS must be a torch tensor or None")
-            if str(dS.dtype) != dt:
-                raise ValueError(f"{who}: dS has dtype {dS.dtype}, the handle holds {dt}")
-            if dS.dim() != 2 or tuple(dS.shape) != (self._nnz, heads):
-                raise ValueError(f"{who}: dS must have shape ({self._nnz}, {heads}), not {tuple(dS.shape)}")
-            if dS.numel() and heads > 1 and dS.stride(1) != 1:
-                raise ValueError(f"{who}: dS must have stride(1) == 1, not {dS.stride()}")
-            if dS.numel() and dS.shape[0] > 1 and dS.stride(0) < heads:
-                raise ValueError(f"{who}: dS rows overlap (stride(0) {dS.stride(0)} < heads = {heads})")
-            for name, t in others:
-                if hasattr(t, "untyped_storage") and dS.numel() and t.numel() and dS.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                    raise ValueError(f"{who}: dS shares a storage with {name} (views of one storage are rejected, disjoint or not)")
-            if dS.device.type != "cuda":
-                raise ValueError(f"{who}: dS must live on the GPU, not {dS.device}")
-            ldds = max(int(dS.stride(0)), heads) if dS.shape[0] > 1 and heads else heads
+        ldds = self._mha_entry_tensor(who, "dS", dS, heads, dt, "the handle holds", others)
+        if dS is not None and dS.device.type != "cuda":
+            raise ValueError(f"{who}: dS must live on the GPU, not {dS.device}")
         return float(scale), ldds
 
     def mhaBiased(self, Q, K, V, O, scale=1.0, slopes=None) -> int:
@@ -521,30 +510,12 @@ class anonymouslibHandle:
             raise ValueError(f"{who}: call inputCSR first")
         if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
             raise ValueError(f"{who}: scale must be a finite Python number, not {scale!r}")
-        lds = []
-        for name, t in (("B", B), ("dB", dB)):
-            if t is None:
-                lds.append(heads)
-                continue
-            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
-                raise ValueError(f"{who}: {name} must be a torch tensor or None")
-            if str(t.dtype) != dt:
-                raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
-            if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
-                raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
-            if t.numel() and heads > 1 and t.stride(1) != 1:
-                raise ValueError(f"{who}: {name} must have stride(1) == 1, not {t.stride()}")
-            if t.numel() and t.shape[0] > 1 and t.stride(0) < heads:
-                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads = {heads})")
-            lds.append(max(int(t.stride(0)), heads) if t.shape[0] > 1 and heads else heads)
-        if dB is not None:
-            for name, t in others + (("B", B),):
-                if hasattr(t, "untyped_storage") and dB.numel() and t.numel() and dB.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                    raise ValueError(f"{who}: dB shares a storage with {name} (views of one storage are rejected, disjoint or not)")
+        ldb = self._mha_entry_tensor(who, "B", B, heads, dt, holds)
+        lddb = self._mha_entry_tensor(who, "dB", dB, heads, dt, holds, others + (("B", B),))
         for name, t in (("B", B), ("dB", dB)):
             if t is not None and t.device.type != "cuda":
                 raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
-        return float(scale), lds[0], lds[1]
+        return float(scale), ldb, lddb
 
     def _mha_edge_device(self, who: str, Q, named) -> None:
         for name, t in named:

@@ -40,9 +40,13 @@ int main(int argc, char **argv)
     memset(dV, 0xFF, s * (size_t)n * lddv);
     memset(work, 0xFF, s * 4 * (size_t)m);
     const bool column = want & 6;
-    int rc = csr5::launch_attention_bwd(A.g, A.da, column ? &At.g : nullptr, column ? &At.da : nullptr, f64 ? CSR5HIP_F64 : CSR5HIP_F32, Q,
-                                        ldq, K, ldk, k, V, ldv, d, dO, lddo, want & 1 ? dQ : nullptr, lddq, want & 2 ? dK : nullptr, lddk,
-                                        want & 4 ? dV : nullptr, lddv, column ? work : nullptr, nullptr);
+    csr5::AttBwdCall c{};
+    c.heads = 1; c.k = k; c.d = d;
+    c.Q = Q; c.ldq = ldq; c.K = K; c.ldk = ldk; c.V = V; c.ldv = ldv; c.dO = dO; c.lddo = lddo;
+    c.dQ = want & 1 ? dQ : nullptr; c.dK = want & 2 ? dK : nullptr; c.dV = want & 4 ? dV : nullptr;
+    c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
+    c.work = column ? work : nullptr; c.gt = column ? &At.g : nullptr; c.dt = column ? &At.da : nullptr;
+    int rc = csr5::launch_mha_bwd(A.g, A.da, f64 ? CSR5HIP_F64 : CSR5HIP_F32, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(dQ, s, (size_t)m * lddq, f);
     fwrite(dK, s, (size_t)n * lddk, f);

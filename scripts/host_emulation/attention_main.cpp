@@ -23,7 +23,10 @@ int main(int argc, char **argv)
     g.m = m; g.n = n; g.nnz = nnz; g.sigma = sigma; g.p = p; g.tile_elems = 64 * sigma;
     csr5::DeviceArrays da{};
     da.row_ptr = rp; da.col = col; da.tile_ptr = tp;
-    int rc = csr5::launch_attention(g, da, f64 ? CSR5HIP_F64 : CSR5HIP_F32, Q, ldq, K, ldk, k, V, ldv, d, O, ldo, nullptr);
+    csr5::AttCall c{};
+    c.heads = 1; c.k = k; c.d = d;
+    c.Q = Q; c.ldq = ldq; c.K = K; c.ldk = ldk; c.V = V; c.ldv = ldv; c.O = O; c.ldo = ldo;
+    int rc = csr5::launch_mha(g, da, f64 ? CSR5HIP_F64 : CSR5HIP_F32, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(O, s, (size_t)m * ldo, f);
     fclose(f);

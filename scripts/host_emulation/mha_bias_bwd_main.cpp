@@ -50,10 +50,14 @@ int main(int argc, char **argv)
     memset(dS, 0xFF, s * (size_t)nnz * ldds);
     memset(work, 0xFF, s * wn);
     const bool column = want & 6;
-    const int rc = csr5::launch_mha_biased_bwd(A.g, A.da, column ? &At.g : nullptr, column ? &At.da : nullptr, f64 ? CSR5HIP_F64 : CSR5HIP_F32,
-                                               heads, groups, scale, has_slopes ? slopes : nullptr, Q, ldq, K, ldk, k, V, ldv, d, dO, lddo,
-                                               want & 1 ? dQ : nullptr, lddq, want & 2 ? dK : nullptr, lddk, want & 4 ? dV : nullptr, lddv,
-                                               column ? work : nullptr, want & 8 ? dS : nullptr, ldds, nullptr);
+    csr5::AttBwdCall c{};
+    c.heads = heads; c.groups = groups; c.k = k; c.d = d; c.scale = scale; c.slopes = has_slopes ? slopes : nullptr;
+    c.Q = Q; c.ldq = ldq; c.K = K; c.ldk = ldk; c.V = V; c.ldv = ldv; c.dO = dO; c.lddo = lddo;
+    c.dQ = want & 1 ? dQ : nullptr; c.dK = want & 2 ? dK : nullptr; c.dV = want & 4 ? dV : nullptr;
+    c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
+    c.work = column ? work : nullptr; c.dS = want & 8 ? dS : nullptr; c.ldds = ldds;
+    c.gt = column ? &At.g : nullptr; c.dt = column ? &At.da : nullptr;
+    const int rc = csr5::launch_mha_biased_bwd(A.g, A.da, f64 ? CSR5HIP_F64 : CSR5HIP_F32, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(dQ, s, (size_t)m * lddq, f);
     fwrite(dK, s, (size_t)n * lddk, f);

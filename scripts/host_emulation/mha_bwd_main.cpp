@@ -1,7 +1,7 @@
 // Stand-alone CPU run of csr5_attention_bwd.hip's multi-head entry on the stand-in runtime of fake/hip/hip_runtime.h: reads a case
 // file written by run_mha.py (header; row_ptr, tile-ordered columns and tile_ptr of the matrix and of its transpose; packed Q, K,
 // V, dO), writes dQ, dK, dV.  heads > 0: launch_mha_bwd with that many heads and `groups` head groups (0: the rule) and a
-// workspace of exactly 4 m heads values.  heads = 0: the single-head launch_attention_bwd on the slices that start offk / offd
+// workspace of exactly 4 m heads values.  heads = 0: the single-head call (launch_mha_bwd, one head) on the slices that start offk / offd
 // columns into the same rows, with a workspace of 4 m values.  Every array is a heap block of its exact size.
 #include "csr5_attention_bwd.hip"
 #include <cstdlib>
@@ -47,14 +47,14 @@ int main(int argc, char **argv)
     const int vt = f64 ? CSR5HIP_F64 : CSR5HIP_F32;
     const csr5::Geometry *gt = column ? &At.g : nullptr;
     const csr5::DeviceArrays *dt = column ? &At.da : nullptr;
-    int rc;
-    if (heads > 0)
-        rc = csr5::launch_mha_bwd(A.g, A.da, gt, dt, vt, heads, groups, Q, ldq, K, ldk, k, V, ldv, d, dO, lddo, want & 1 ? dQ : nullptr, lddq,
-                                  want & 2 ? dK : nullptr, lddk, want & 4 ? dV : nullptr, lddv, column ? work : nullptr, nullptr);
-    else
-        rc = csr5::launch_attention_bwd(A.g, A.da, gt, dt, vt, Q + s * offk, ldq, K + s * offk, ldk, k, V + s * offd, ldv, d, dO + s * offd,
-                                        lddo, want & 1 ? dQ + s * offk : nullptr, lddq, want & 2 ? dK + s * offk : nullptr, lddk,
-                                        want & 4 ? dV + s * offd : nullptr, lddv, column ? work : nullptr, nullptr);
+    csr5::AttBwdCall c{};
+    c.k = k; c.d = d; c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.lddo = lddo; c.lddq = lddq; c.lddk = lddk; c.lddv = lddv;
+    c.work = column ? work : nullptr; c.gt = gt; c.dt = dt;
+    const size_t ok = heads > 0 ? 0 : s * offk, od = heads > 0 ? 0 : s * offd; // heads <= 0: the single-head call on one head's slices
+    c.heads = heads > 0 ? heads : 1; c.groups = heads > 0 ? groups : 0;
+    c.Q = Q + ok; c.K = K + ok; c.V = V + od; c.dO = dO + od;
+    c.dQ = want & 1 ? dQ + ok : nullptr; c.dK = want & 2 ? dK + ok : nullptr; c.dV = want & 4 ? dV + od : nullptr;
+    const int rc = csr5::launch_mha_bwd(A.g, A.da, vt, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(dQ, s, (size_t)m * lddq, f);
     fwrite(dK, s, (size_t)n * lddk, f);

@@ -41,17 +41,19 @@ int main(int argc, char **argv)
     g.m = m; g.n = n; g.nnz = nnz; g.sigma = sigma; g.p = p; g.tile_elems = 64 * sigma;
     csr5::DeviceArrays da{};
     da.row_ptr = rp; da.col = col; da.tile_ptr = tp; da.val = nullptr;
-    int rc = csr5::launch_mha_lowp(g, da, bf16 ? CSR5HIP_BF16 : CSR5HIP_F16, heads, groups, scale, has_b ? B : nullptr, ldb, Q, ldq, K, ldk, k,
-                                   V, ldv, d, O, ldo, nullptr);
+    csr5::AttCall c{};
+    c.heads = heads; c.groups = groups; c.k = k; c.d = d; c.scale = scale; c.B = has_b ? B : nullptr; c.ldb = ldb;
+    c.Q = Q; c.ldq = ldq; c.K = K; c.ldk = ldk; c.V = V; c.ldv = ldv; c.O = O; c.ldo = ldo;
+    int rc = csr5::launch_mha_lowp(g, da, bf16 ? CSR5HIP_BF16 : CSR5HIP_F16, c, nullptr);
     float *B32 = bf16 ? widened<__bf16>(B, count(nnz, ldb)) : widened<_Float16>(B, count(nnz, ldb));
     float *Q32 = bf16 ? widened<__bf16>(Q, count(m, ldq)) : widened<_Float16>(Q, count(m, ldq));
     float *K32 = bf16 ? widened<__bf16>(K, count(n, ldk)) : widened<_Float16>(K, count(n, ldk));
     float *V32 = bf16 ? widened<__bf16>(V, count(n, ldv)) : widened<_Float16>(V, count(n, ldv));
     float *O32 = (float *)malloc(4 * (count(m, ldo) ? count(m, ldo) : 1));
     memset(O32, 0xFF, 4 * count(m, ldo));
+    c.B = has_b ? B32 : nullptr; c.Q = Q32; c.K = K32; c.V = V32; c.O = O32;
     if (!rc)
-        rc = csr5::launch_mha_edge(g, da, CSR5HIP_F32, heads, groups, scale, has_b ? B32 : nullptr, ldb, Q32, ldq, K32, ldk, k, V32, ldv, d,
-                                   O32, ldo, nullptr);
+        rc = csr5::launch_mha_edge(g, da, CSR5HIP_F32, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(O, 2, count(m, ldo), f);
     fwrite(O32, 4, count(m, ldo), f);

@@ -1,6 +1,6 @@
 // Stand-alone CPU run of csr5_attention.hip's multi-head entry on the stand-in runtime of fake/hip/hip_runtime.h: reads a case file
 // written by run_mha.py (header, row_ptr, tile-ordered columns, tile_ptr, packed Q, K, V), writes O.  heads > 0: launch_mha with
-// that many heads and `groups` head groups (0: the rule).  heads = 0: the single-head launch_attention on the slices that start
+// that many heads and `groups` head groups (0: the rule).  heads = 0: the single-head call (launch_mha, one head) on the slices that start
 // offk / offd columns into the same rows.  Every array is a heap block of its exact size, so -fsanitize=address sees any access
 // outside it.
 #include "csr5_attention.hip"
@@ -27,11 +27,14 @@ int main(int argc, char **argv)
     csr5::DeviceArrays da{};
     da.row_ptr = rp; da.col = col; da.tile_ptr = tp;
     const int vt = f64 ? CSR5HIP_F64 : CSR5HIP_F32;
-    int rc;
-    if (heads > 0)
-        rc = csr5::launch_mha(g, da, vt, heads, groups, Q, ldq, K, ldk, k, V, ldv, d, O, ldo, nullptr);
-    else
-        rc = csr5::launch_attention(g, da, vt, Q + s * offk, ldq, K + s * offk, ldk, k, V + s * offd, ldv, d, O + s * offd, ldo, nullptr);
+    csr5::AttCall c{};
+    c.k = k; c.d = d; c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldo = ldo;
+    if (heads > 0) {
+        c.heads = heads; c.groups = groups; c.Q = Q; c.K = K; c.V = V; c.O = O;
+    } else { // the single-head call on one head's slices
+        c.heads = 1; c.Q = Q + s * offk; c.K = K + s * offk; c.V = V + s * offd; c.O = O + s * offd;
+    }
+    const int rc = csr5::launch_mha(g, da, vt, c, nullptr);
     f = fopen(argv[2], "wb");
     fwrite(O, s, (size_t)m * ldo, f);
     fclose(f);
