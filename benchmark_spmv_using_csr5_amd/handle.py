@@ -672,7 +672,8 @@ class anonymouslibHandle:
         if not val.is_contiguous():
             raise ValueError(f"updateValues: val must be contiguous, not stride {val.stride()}")
         mine = self._keep.get("val")
-        if hasattr(mine, "untyped_storage") and val.untyped_storage().data_ptr() == mine.untyped_storage().data_ptr():
+        # (tensors without elements own no memory: their storages all report the same null pointer and alias nothing)
+        if val.numel() and hasattr(mine, "untyped_storage") and val.untyped_storage().data_ptr() == mine.untyped_storage().data_ptr():
             raise ValueError("updateValues: val shares storage with the tensor given to inputCSR (aliased)")
         if val.device.type != "cuda":
             raise ValueError(f"updateValues: val must live on the GPU, not {val.device}")
