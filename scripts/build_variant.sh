@@ -9,7 +9,7 @@ out=/tmp/csr5_variant_$name
 mkdir -p $out
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno-unused-function -I$root/include -I$src -DCSR5_FEW_SIGMAS $flags"
 pids=()
-for f in csr5_format csr5_capi csr5_ingest csr5_slab csr5_multi csr5_hot; do
+for f in csr5_format csr5_capi csr5_convert csr5_checkpoint csr5_slab_build csr5_ingest csr5_slab csr5_multi csr5_hot; do
   /opt/rocm/bin/hipcc $HIPFLAGS -c $src/$f.hip -o $out/$f.o & pids+=($!)
 done
 /opt/rocm/bin/hipcc $HIPFLAGS -DCSR5_SPMV_ONLY_F64 -c $src/csr5_spmv.hip -o $out/csr5_spmv_f64.o & pids+=($!)

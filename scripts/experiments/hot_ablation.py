@@ -95,7 +95,7 @@ def main():
                  f"-I{ROOT}/include", f"-I{tmp}", "-DCSR5_FEW_SIGMAS"]
         objs = []
         procs = []
-        for f in ("csr5_format", "csr5_capi", "csr5_ingest", "csr5_slab", "csr5_multi", "csr5_hot"):
+        for f in ("csr5_format", "csr5_capi", "csr5_convert", "csr5_checkpoint", "csr5_slab_build", "csr5_ingest", "csr5_slab", "csr5_multi", "csr5_hot"):
             o = os.path.join(tmp, f + ".o")
             objs.append(o)
             procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", *flags, "-c", os.path.join(tmp, f + ".hip"), "-o", o]))
