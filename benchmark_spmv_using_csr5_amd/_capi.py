@@ -217,6 +217,15 @@ SYMBOLS_LOWP = [
                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
 ]
 
+# its backward, bound by load() like the others: the operand type, then csr5hip_mha_edge_bias_backward's arguments.  A list of its own:
+# tests/test_mha_lowp_host.py pins SYMBOLS_LOWP to its one entry and tests/test_attention_entry_points_host.py the four lists above
+# to nine attention names; tests/test_mha_lowp_backward_host.py compares this one with the export and the header.
+SYMBOLS_LOWP_BACKWARD = [
+    ("csr5hip_mha_lowp_backward", C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+]
+
 _lib = None
 
 
@@ -239,7 +248,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

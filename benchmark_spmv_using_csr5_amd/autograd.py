@@ -40,7 +40,8 @@ nnz values in CSR order and is given to the handle as ``spmm``'s ``val`` is, so 
 shape (nnz, H) -- a learned edge bias that differs per head -- takes ``A.mhaEdgeBias`` / ``A.mhaEdgeBiasBackward`` instead: the
 bias stays the caller's tensor, the handle is given no values and nothing about it is recorded or checked.  With bf16 or fp16
 Q, K, V (and such a 2-D bias) the forward is one ``A.mhaLowp`` -- 16-bit operands, fp32 arithmetic, whatever the handle's dtype --
-and the backward widens what was kept and goes through ``A.mhaEdgeBiasBackward`` (a stopgap, see ``multihead_attention``).
+and the backward on an fp32 handle is one ``A.mhaLowpBackward`` on the kept 16-bit tensors (no widened copy, no cast); on an fp64
+handle it still widens what was kept and goes through ``A.mhaEdgeBiasBackward`` (a stopgap, see ``multihead_attention``).
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -397,9 +398,11 @@ class _EdgeBiasMultiheadAttention(torch.autograd.Function):
 
 
 class _LowpMultiheadAttention(torch.autograd.Function):
-    """bf16 / fp16 operands: the forward is ONE ``A.mhaLowp``; the backward is a STOPGAP until there is a 16-bit backward kernel:
-    the saved operands and dO are widened to the handle's dtype, ``A.mhaEdgeBiasBackward`` computes the gradients there, and each
-    wanted one is cast to its input's dtype."""
+    """bf16 / fp16 operands: the forward is ONE ``A.mhaLowp``.  On an fp32 handle the backward is ONE ``A.mhaLowpBackward`` on the
+    kept 16-bit tensors and on dO as it arrives: 16-bit outputs for exactly the inputs that need a gradient, a float32 workspace
+    only when K or V needs one, dB the bias gradient itself.  On an fp64 handle the backward stays the STOPGAP it was: the saved
+    operands and dO are widened to fp64, ``A.mhaEdgeBiasBackward`` computes the gradients there, and each wanted one is cast to
+    its input's dtype (moving it to the fp32 kernel would change gradient bits)."""
 
     @staticmethod
     def forward(ctx, A, Q, K, V, scale, bias):
@@ -419,9 +422,23 @@ class _LowpMultiheadAttention(torch.autograd.Function):
         if not (any(need) or need_bias):
             return (None,) * 6
         A = ctx.A
+        if A._vt != _capi.F64:
+            Q, K, V = ctx.saved_tensors[:3]
+            B = ctx.saved_tensors[3] if ctx.has_bias else None
+            dO = _packed(dO.detach())
+            _on_current_stream(A, dO.device)
+            outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
+            work = None
+            if need[1] or need[2]:
+                if not A.info().transpose_built:
+                    _check(A.buildTranspose(), "buildTranspose")
+                work = torch.empty(4 * A._m * Q.shape[1], dtype=torch.float32, device=dO.device)
+            dB = torch.empty(tuple(B.shape), dtype=B.dtype, device=dO.device) if need_bias else None  # (every element is written)
+            _check(A.mhaLowpBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaLowpBackward")
+            return (None,) + tuple(outs) + (None, dB)  # (dB IS the gradient of the bias: no reduction, no cast)
         low = ctx.saved_tensors[0].dtype
-        wide = torch.float64 if A._vt == _capi.F64 else torch.float32
-        Q, K, V = (t.to(wide) for t in ctx.saved_tensors[:3])  # (a temporary each: what the 16-bit backward kernel will save)
+        wide = torch.float64
+        Q, K, V = (t.to(wide) for t in ctx.saved_tensors[:3])  # (a temporary each: what the fp32 handle's route does not make)
         B = ctx.saved_tensors[3].to(wide) if ctx.has_bias else None
         dO = _packed(dO.detach()).to(wide)
         _on_current_stream(A, dO.device)
@@ -479,9 +496,13 @@ def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     A ``torch.bfloat16`` or ``torch.float16`` Q takes the 16-BIT ROUTE, whatever the handle's dtype: K, V and ``bias`` (``None`` or
     2-D (nnz, H)) have Q's dtype, forward is ONE ``A.mhaLowp`` -- fp32 arithmetic, O rounded once, the handle's values not read --
     and Q, K, V and the bias are kept.  A 1-D bias or ``slopes`` raises ValueError there: those live in the handle's values, which
-    have another type.  BACKWARD IS A STOPGAP until a 16-bit backward kernel exists: the kept tensors and the incoming gradient are
-    widened to the handle's dtype, ONE ``A.mhaEdgeBiasBackward`` runs on them, and each wanted gradient is cast to its input's
-    dtype; on an fp32 handle the recomputed scores are the forward's bits.  There is no ``torch.autocast`` integration."""
+    have another type.  BACKWARD ON AN fp32 HANDLE is ONE ``A.mhaLowpBackward`` (two launches) on the kept 16-bit tensors and on the
+    incoming gradient as it arrives: ``torch.empty`` 16-bit outputs for exactly the inputs that need a gradient, a float32
+    workspace of 4 m H values and the transposed companion only when K or V needs one, ``grad_bias`` the dB the kernel writes; no
+    widened copy and no cast.  Each gradient is the fp32 route's on the widened operands rounded once, and the recomputed scores
+    are the forward's bits.  ON AN fp64 HANDLE THE BACKWARD IS STILL A STOPGAP: the kept tensors and the incoming gradient are
+    widened to fp64, ONE ``A.mhaEdgeBiasBackward`` runs on them, and each wanted gradient is cast to its input's dtype.  There is
+    no ``torch.autocast`` integration."""
     if getattr(Q, "dtype", None) in (torch.bfloat16, torch.float16):
         if slopes is not None or (bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2)):
             raise ValueError("multihead_attention: with bf16 / fp16 operands the bias is None or a 2-D (nnz, H) tensor of their dtype; a "

@@ -2,6 +2,11 @@
 // contract is written out at the head of csr5_attention_bwd.hip.  Two translation units instantiate them: csr5_attention_bwd.hip
 // the plain entry points (AttBwdArgs), csr5_attention_bwd_bias.hip the biased one (csr5hip_mha_biased_backward; AttBwdBiasArgs),
 // csr5_attention_bwd_edge.hip the edge-biased one (csr5hip_mha_edge_bias_backward; AttBwdEdgeArgs: ARGS::EDGE).
+// csr5_attention_bwd_lowp.hip instantiates them a fourth time with operands and outputs STORED in bf16 or fp16 and float arithmetic
+// (csr5hip_mha_lowp_backward; AttBwdLowpArgs, k_attention_bwd_lowp): ARGS::ST is the type behind the operand and output pointers, VT
+// the type of everything computed, of the workspace, the LDS stage and the reductions.  Where ST == VT the casts between them and
+// att_stored are no operation, and the kernels of the other units are, instruction for instruction, what they were without them
+// (scripts/compare_attention_asm.py).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED), as in csr5_attention_kern.h: the plain instantiations
 // carry no argument, no branch and no load for it.  Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
 #pragma once
@@ -14,6 +19,7 @@ template <typename VT>
 struct AttBwdArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's rank in the parent's CSR order)
+    using ST = VT;                      // the type behind the operand and output pointers (AttBwdLowpArgs: another one than VT)
     int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
     unsigned recip;
@@ -50,6 +56,32 @@ struct AttBwdEdgeArgs : AttBwdArgs<VT> {
     static constexpr bool EDGE = true;
     AttEdgeBias<VT> bias;
     VT *dS;
+    int ldds;
+};
+
+// csr5hip_mha_lowp_backward (csr5_attention_bwd_lowp.hip): AttBwdEdgeArgs<float>'s call with Q, K, V, B and dO STORED in ST (bf16 or
+// fp16) and dQ, dK, dV and dB written in it.  The arithmetic, the LDS stage, the reductions and the workspace are float: the templates
+// below widen an operand where they load it and round an output once where they store it (att_stored), and are otherwise the float
+// instantiation's, statement for statement.  A struct of its own: the existing ones keep their layouts, and their kernels their code.
+template <typename ST_>
+struct AttBwdLowpArgs {
+    static constexpr bool BIASED = true;
+    static constexpr bool EDGE = true;
+    using ST = ST_;
+    int lines, k, d;
+    int T, sigma, tiles;
+    unsigned recip;
+    const int32_t *row_ptr;
+    const int32_t *col;
+    const uint32_t *tile_ptr;
+    const ST *Q, *K, *V, *dO;
+    ST *dQ, *dK, *dV;
+    float *work; // unrounded: the column kernel reads back the row kernel's M, 1 / Z and D
+    int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
+    int heads, hper;
+    int ws;
+    AttEdgeBiasLowpMap<ST> bias;
+    ST *dS;
     int ldds;
 };
 
@@ -116,7 +148,7 @@ __device__ __forceinline__ void bwd_store_ds(const ARGS &A, const int t0, const 
 {
     if constexpr (ARGS::BIASED)
         if (A.dS)
-            A.dS[((size_t)t0 * A.T + (size_t)rem0 + (size_t)j) * A.ldds] = ds;
+            A.dS[((size_t)t0 * A.T + (size_t)rem0 + (size_t)j) * A.ldds] = att_stored<typename ARGS::ST>(ds);
 }
 
 // the score of the entry (i, j) alone; av: its value (read only when biased)
@@ -153,9 +185,9 @@ __device__ __forceinline__ void bwd_entry_col(const ARGS &A, const size_t i, con
 
 // ---- accumulation, L <= 16: ONE chain per output column over the entries in ascending order.  coef / idx: lane sub * 16 + e
 // holds the coefficient and the operand row of entry e; out: the output row (used where rowok)
-template <typename VT>
+template <typename VT, typename ST>
 __device__ __forceinline__ void bwd_short_acc(const bool rowok, const int rl, const int sub, const int pos, const VT coef, const int idx,
-                                              const VT *__restrict__ X, const int ldx, const int width, VT *out)
+                                              const ST *__restrict__ X, const int ldx, const int width, ST *out)
 {
     constexpr int G = AT_G;
     for (int cb = 0; cb < width; cb += G) { // (uniform)
@@ -167,17 +199,17 @@ __device__ __forceinline__ void bwd_short_acc(const bool rowok, const int rl, co
             const VT we = __shfl(coef, sub * G + e, OMEGA);
             const int je = __shfl(idx, sub * G + e, OMEGA);
             if (rowok && e < rl && c < width)
-                acc = fma_vt(we, X[(size_t)(uint32_t)je * ldx + c], acc);
+                acc = fma_vt(we, (VT)X[(size_t)(uint32_t)je * ldx + c], acc);
         }
         if (rowok && c < width)
-            out[c] = acc;
+            out[c] = att_stored<ST>(acc);
     }
 }
 
 // ---- accumulation, 17 <= L <= 512: the forward's wavefront rule; coef / idx: the wavefront's staged entries in LDS
-template <typename VT>
-__device__ __forceinline__ void bwd_wave_acc(const VT *coef, const int *idx, const int rl, const VT *__restrict__ X, const int ldx,
-                                             const int width, VT *out)
+template <typename VT, typename ST>
+__device__ __forceinline__ void bwd_wave_acc(const VT *coef, const int *idx, const int rl, const ST *__restrict__ X, const int ldx,
+                                             const int width, ST *out)
 {
     const int lane = threadIdx.x & (OMEGA - 1);
     for (int cb = 0; cb < width; cb += OMEGA) {
@@ -186,24 +218,24 @@ __device__ __forceinline__ void bwd_wave_acc(const VT *coef, const int *idx, con
         const int slot = lane / C, cc = lane & (C - 1);
         VT acc = (VT)0;
         if (cc < wb) {
-            const VT *x = X + cb + cc;
+            const ST *x = X + cb + cc;
 #pragma unroll 4
             for (int e = slot; e < rl; e += S)
-                acc = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], acc);
+                acc = fma_vt(coef[e], (VT)x[(size_t)(uint32_t)idx[e] * ldx], acc);
         }
         for (int off = C; off < OMEGA; off <<= 1) // (uniform; adjacent slots first)
             acc += __shfl_xor(acc, off, OMEGA);
         if (slot == 0 && cc < wb)
-            out[cb + cc] = acc;
+            out[cb + cc] = att_stored<ST>(acc);
     }
 }
 
 // ---- accumulation, L > 512: the forward's workgroup rule.  staged: coef / idx hold all rl entries (filled by the caller; the
 // barrier below publishes them); otherwise fill(base, n) writes entries base .. base + n - 1 to coef / idx [0, n) chunk by chunk,
 // again for every 256 output columns.  Ends with a barrier: the stage is free.
-template <typename VT, typename FILL>
+template <typename VT, typename FILL, typename ST>
 __device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FILL fill, const VT *coef, const int *idx,
-                                            const VT *__restrict__ X, const int ldx, const int width, VT *out, VT *red)
+                                            const ST *__restrict__ X, const int ldx, const int width, ST *out, VT *red)
 {
     const int tid = (int)threadIdx.x;
     for (int cg = 0; cg < width; cg += OMEGA * AT_HUB_BLOCKS) {
@@ -226,11 +258,11 @@ __device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FIL
                     const int C = att_pow2(wb), S = AT_BLOCK / C; // (AT_STAGE is a multiple of S: a chunk keeps j mod S)
                     const int slot = tid / C, cc = tid & (C - 1);
                     if (cc < wb) {
-                        const VT *x = X + cb + cc;
+                        const ST *x = X + cb + cc;
                         VT o = acc[b];
 #pragma unroll 4
                         for (int e = slot; e < n; e += S)
-                            o = fma_vt(coef[e], x[(size_t)(uint32_t)idx[e] * ldx], o);
+                            o = fma_vt(coef[e], (VT)x[(size_t)(uint32_t)idx[e] * ldx], o);
                         acc[b] = o;
                     }
                 }
@@ -248,7 +280,7 @@ __device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FIL
                 red[tid] = o;
                 __syncthreads();
                 if (tid < wb) // ... then (w0 + w1) + (w2 + w3); lane c < C of every wavefront holds column c
-                    out[cb + tid] = (red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid]);
+                    out[cb + tid] = att_stored<ST>((red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid]));
                 __syncthreads(); // (red is free for the next block)
             }
         }
@@ -607,6 +639,21 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_edge(const AttBwdEdg
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }
 
+// 16-bit operands and outputs, float arithmetic: always the packed, edge-biased call.  6 waves per SIMD are
+// k_attention_bwd_edge<float, ..>'s: left to itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 81
+// (row kernel) and 82 (column kernel) registers with 16-byte loads, which are 5 waves
+#if defined(__HIP__)
+#define CSR5_ATT_BWD_LOWP_WAVES __attribute__((amdgpu_waves_per_eu(6)))
+#else // (the host emulation compiles this header as plain C++, where no function is a kernel)
+#define CSR5_ATT_BWD_LOWP_WAVES
+#endif
+template <typename ST, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_BWD_LOWP_WAVES k_attention_bwd_lowp(const AttBwdLowpArgs<ST> A)
+{
+    using VT = float;
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+
 // the kernels of an argument struct, as overloads (csr5_attention_kern.h attention_enqueue).  COL: the column kernel
 template <bool VEC, bool COL, bool MH, typename VT>
 static void attention_bwd_enqueue(const AttBwdArgs<VT> &A, const dim3 grid, hipStream_t s)
@@ -624,10 +671,16 @@ static void attention_bwd_enqueue(const AttBwdEdgeArgs<VT> &A, const dim3 grid, 
     hipLaunchKernelGGL((k_attention_bwd_edge<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 
+template <bool VEC, bool COL, bool MH, typename ST>
+static void attention_bwd_enqueue(const AttBwdLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_lowp<ST, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+
 // the pattern walked and the head groups of one side's launch.  groups: the head groups over grid.y, 0 for the rule
 // (att_heads_per_group of this side's line count)
-template <typename VT>
-static void attention_bwd_fill(AttBwdArgs<VT> &A, const Geometry &g, const DeviceArrays &d, const int groups)
+template <typename ARGS>
+static void attention_bwd_fill(ARGS &A, const Geometry &g, const DeviceArrays &d, const int groups)
 {
     A.lines = g.m;
     A.hper = groups > 0 ? (A.heads + groups - 1) / groups : att_heads_per_group(g.m, A.heads);
@@ -661,10 +714,10 @@ static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, A
 {
     if (g.m <= 0 || A.heads <= 0)
         return hipSuccess;
-    attention_bwd_fill<VT>(A, g, d, c.groups);
+    attention_bwd_fill(A, g, d, c.groups);
     if constexpr (ARGS::BIASED)
         att_set_bias(A.bias, d, map, c);
-    const bool vec = attention_bwd_vec<VT>(c.heads, c.k, c.d, c.Q, c.ldq, c.K, c.ldk, c.V, c.ldv, c.dO, c.lddo);
+    const bool vec = attention_bwd_vec<typename ARGS::ST>(c.heads, c.k, c.d, c.Q, c.ldq, c.K, c.ldk, c.V, c.ldv, c.dO, c.lddo);
     const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
     if (A.heads == 1) {
         const dim3 grid(blocks);
@@ -683,21 +736,23 @@ static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, A
 }
 
 // The launcher of every backward unit: ARGS is the unit's argument struct (AttBwd..Args<VT>), which decides the kernels
-// (attention_bwd_enqueue) and the bias fields (att_set_bias).  g / d: the parent's pattern (the row kernel); c.gt / c.dt (edge: and
-// c.map): the transposed companion's (the column kernel, only when dK or dV is wanted).  The row kernel runs when dQ or dS is wanted
-// or the column kernel needs the workspace; dS is the row side's alone.
+// (attention_bwd_enqueue) and the bias fields (att_set_bias); VT: the type computed in and of the workspace, ARGS::ST the operands'
+// and the outputs'.  g / d: the parent's pattern (the row kernel); c.gt / c.dt (edge: and c.map): the transposed companion's (the
+// column kernel, only when dK or dV is wanted).  The row kernel runs when dQ or dS is wanted or the column kernel needs the
+// workspace; dS is the row side's alone.
 template <typename VT, typename ARGS>
 hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const AttBwdCall &c, hipStream_t s)
 {
+    using ST = typename ARGS::ST;
     ARGS A{};
     A.k = c.k;
     A.d = c.d;
     A.heads = c.heads;
     A.ws = 4 * c.heads;
-    A.Q = (const VT *)c.Q;
-    A.K = (const VT *)c.K;
-    A.V = (const VT *)c.V;
-    A.dO = (const VT *)c.dO;
+    A.Q = (const ST *)c.Q;
+    A.K = (const ST *)c.K;
+    A.V = (const ST *)c.V;
+    A.dO = (const ST *)c.dO;
     A.ldq = c.ldq;
     A.ldk = c.ldk;
     A.ldv = c.ldv;
@@ -712,10 +767,10 @@ hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const 
     hipError_t e = hipSuccess;
     if (c.dQ || dS || column) {
         ARGS R = A;
-        R.dQ = c.k > 0 ? (VT *)c.dQ : nullptr;
+        R.dQ = c.k > 0 ? (ST *)c.dQ : nullptr;
         R.work = column ? (VT *)c.work : nullptr;
         if constexpr (ARGS::BIASED) {
-            R.dS = (VT *)dS;
+            R.dS = (ST *)dS;
             R.ldds = c.ldds;
         }
         if (R.dQ || R.work || dS)
@@ -723,8 +778,8 @@ hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const 
     }
     if (e == hipSuccess && column) {
         ARGS C = A;
-        C.dK = c.k > 0 ? (VT *)c.dK : nullptr;
-        C.dV = c.d > 0 ? (VT *)c.dV : nullptr;
+        C.dK = c.k > 0 ? (ST *)c.dK : nullptr;
+        C.dV = c.d > 0 ? (ST *)c.dV : nullptr;
         C.work = (VT *)c.work;
         if (C.dK || C.dV)
             e = attention_bwd_side<true, VT>(*c.gt, *c.dt, C, c.map, c, s);

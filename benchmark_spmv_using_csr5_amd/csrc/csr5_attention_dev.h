@@ -176,6 +176,35 @@ __device__ __forceinline__ float att_bias_score(const AttEdgeBiasLowp<ST> &E, co
     return fma_vt(qk, E.c, b);
 }
 
+// Its sibling for the backward (csr5hip_mha_lowp_backward, csr5_attention_bwd_lowp.hip), whose column kernel needs the companion's
+// source map as AttEdgeBias does.  A struct of its own: the forward's has no map and keeps its layout, and k_attention_lowp its
+// kernarg block and its code.
+template <typename ST>
+struct AttEdgeBiasLowpMap {
+    const ST *B;
+    const uint32_t *map;
+    int ldb;
+    float c;
+};
+
+template <typename ST>
+__device__ __forceinline__ size_t att_edge_rank(const AttEdgeBiasLowpMap<ST> &E, const size_t q)
+{
+    return E.map ? (size_t)E.map[q] : q;
+}
+
+template <typename ST>
+__device__ __forceinline__ float att_edge_value(const AttEdgeBiasLowpMap<ST> &E, const size_t e, const int h)
+{
+    return E.B ? (float)E.B[e * (size_t)E.ldb + (size_t)h] : 0.0f;
+}
+
+template <typename ST>
+__device__ __forceinline__ float att_bias_score(const AttEdgeBiasLowpMap<ST> &E, const int, const float qk, const float b)
+{
+    return fma_vt(qk, E.c, b);
+}
+
 // The variant-specific part of a launch, forward and backward alike: the bias fields from the call.  side: the arrays of the pattern
 // the kernel walks (the parent's, or the companion's in the column kernel); map: null where that pattern is the parent's, the
 // companion's source map in the column kernel.
@@ -199,6 +228,15 @@ static void att_set_bias(AttEdgeBiasLowp<ST> &b, const DeviceArrays &, const uin
 {
     static_assert(sizeof(ST) == 2, "a 16-bit operand type");
     b.B = (const ST *)c.B;
+    b.ldb = c.ldb;
+    b.c = (float)c.scale;
+}
+template <typename ST>
+static void att_set_bias(AttEdgeBiasLowpMap<ST> &b, const DeviceArrays &, const uint32_t *map, const AttCall &c)
+{
+    static_assert(sizeof(ST) == 2, "a 16-bit operand type");
+    b.B = (const ST *)c.B;
+    b.map = map;
     b.ldb = c.ldb;
     b.c = (float)c.scale;
 }

@@ -489,7 +489,7 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
 }
 
 // ---- attention on the pattern (csr5_attention*.hip) ---------------------------------------------------------------------------
-// The nine entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
+// The ten entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
 // trivial cases, the launch.  The single-head calls are heads = 1.  The forward reads row_ptr, tile_ptr and the tile-ordered
 // column_index of the parent, whatever path spmv() takes (biased: its tile-ordered values too); it allocates nothing and changes
 // nothing: enqueue-only.  lowp: the call names the type its operands are stored in (operand_type, judged here); the others take the handle's.
@@ -529,10 +529,15 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
 // The backward in two launches: the row kernel on the parent's pattern (it writes dQ, and dS / dB when given), the column kernel on
 // the transposed companion's (dK, dV; edge: it finds an entry's rank through the companion's source map, comp[A_MAP], passed, not
 // copied).  Allocates nothing, changes nothing of the handle or of its companion: enqueue-only.  c: everything but gt, dt and map,
-// which come from the handle.
-static int attention_backward(csr5hip_handle h, const char *name, AttVariant variant, AttBwdCall c)
+// which come from the handle.  lowp: as in attention_forward; the operands, the outputs and the zeros of the trivial case are 2-byte
+// elements then, the workspace float.
+static int attention_backward(csr5hip_handle h, const char *name, AttVariant variant, bool lowp, int operand_type, AttBwdCall c)
 {
-    if (!h || c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
+    if (!h)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
+        return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
         return CSR5HIP_INVALID_ARGUMENT;
     const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
     if (c.ldq < wk || c.ldk < wk || c.lddq < wk || c.lddk < wk || c.ldv < wd || c.lddo < wd || c.lddv < wd ||
@@ -553,7 +558,7 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         return CSR5HIP_UNKOWN_FORMAT;
     if (!any || c.heads == 0)
         return CSR5HIP_SUCCESS;
-    const size_t vs = h->vsize();
+    const size_t vs = lowp ? 2 : h->vsize(); // (lowp: the word 0x0000 is +0 in both 16-bit types)
     // no entries (and then no companion arrays, and no element of dS / dB): the zeros
     if (nnz == 0 || (column && (!h->comp.at || (variant == ATT_EDGE && !h->comp[A_MAP].ptr)))) {
         if (c.dQ && c.k > 0 && h->g.m > 0)
@@ -569,7 +574,9 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         c.dt = &h->comp.at->d;
         c.map = variant == ATT_EDGE ? (const uint32_t *)h->comp[A_MAP].ptr : nullptr;
     }
-    if (variant == ATT_PLAIN)
+    if (lowp)
+        HIP_TRY(launch_mha_lowp_bwd(h->g, h->d, operand_type, c, h->stream));
+    else if (variant == ATT_PLAIN)
         HIP_TRY(launch_mha_bwd(h->g, h->d, h->value_type, c, h->stream));
     else if (variant == ATT_BIASED)
         HIP_TRY(launch_mha_biased_bwd(h->g, h->d, h->value_type, c, h->stream));
@@ -606,7 +613,7 @@ int csr5hip_attention_backward(csr5hip_handle h, const void *d_Q, int ldq, const
                                void *d_work)
 {
     const AttBwdCall c = att_bwd_call(1, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
-    return attention_backward(h, "csr5hip_attention_backward", ATT_PLAIN, c);
+    return attention_backward(h, "csr5hip_attention_backward", ATT_PLAIN, false, 0, c);
 }
 
 // `heads` heads on packed operands in one launch (the head loop inside the row classes)
@@ -621,7 +628,7 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads, const void *d_Q, int ldq, 
                          void *d_work)
 {
     const AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
-    return attention_backward(h, "csr5hip_mha_backward", ATT_PLAIN, c);
+    return attention_backward(h, "csr5hip_mha_backward", ATT_PLAIN, false, 0, c);
 }
 
 // the score fma(qk, scale, slopes[h] * value of the entry): reads the parent's tile-ordered values next to its columns (the column
@@ -640,7 +647,7 @@ int csr5hip_mha_biased_backward(csr5hip_handle h, int heads, double scale, const
 {
     AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
     c.scale = scale; c.slopes = d_slopes; c.dS = d_dS; c.ldds = ldds;
-    return attention_backward(h, "csr5hip_mha_biased_backward", ATT_BIASED, c);
+    return attention_backward(h, "csr5hip_mha_biased_backward", ATT_BIASED, false, 0, c);
 }
 
 // the score fma(qk, scale, B[e * ldb + h]), B a caller's tensor in CSR order: reads the parent's pattern and nothing of its values
@@ -668,7 +675,18 @@ int csr5hip_mha_edge_bias_backward(csr5hip_handle h, int heads, double scale, co
 {
     AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
     c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
-    return attention_backward(h, "csr5hip_mha_edge_bias_backward", ATT_EDGE, c);
+    return attention_backward(h, "csr5hip_mha_edge_bias_backward", ATT_EDGE, false, 0, c);
+}
+
+// csr5hip_mha_edge_bias_backward on operands and gradients stored in bf16 / fp16, computed in float (csr5_attention_bwd_lowp.hip):
+// the handle's value type plays no part, and d_work is float whatever it is
+int csr5hip_mha_lowp_backward(csr5hip_handle h, int operand_type, int heads, double scale, const void *d_B, int ldb, const void *d_Q,
+                              int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo,
+                              void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dB, int lddb)
+{
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
+    return attention_backward(h, "csr5hip_mha_lowp_backward", ATT_EDGE, true, operand_type, c);
 }
 
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------

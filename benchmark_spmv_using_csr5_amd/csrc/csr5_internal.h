@@ -307,6 +307,10 @@ hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand
 hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_mha_edge_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+// csr5_attention_bwd_lowp.hip: launch_mha_edge_bwd on operands stored in 16 bits (operand_type: CSR5HIP_BF16 or CSR5HIP_F16, checked by
+// the caller; B, Q, K, V, dO and dQ, dK, dV, dS all of that type, leading dimensions in its elements), float arithmetic, every output
+// rounded once; c.work is FLOAT, 4 m heads values.  Neither d.val nor c.dt->val is read
+hipError_t launch_mha_lowp_bwd(const Geometry &g, const DeviceArrays &d, int operand_type, const AttBwdCall &c, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

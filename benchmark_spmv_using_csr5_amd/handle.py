@@ -306,11 +306,12 @@ class anonymouslibHandle:
                                                     _ptr(work))
 
     # -- attention for all heads in one launch (csr5hip.h csr5hip_mha / csr5hip_mha_backward) -------
-    def _mha_args(self, who: str, ins, outs, work, dt=None):
+    def _mha_args(self, who: str, ins, outs, work, dt=None, work_dt=None):
         """the checks of ``attention``'s operands for packed 3-D tensors (rows, heads, width): ValueError, naming the operand,
         unless each has the handle's dtype, its row count, stride(2) == 1, stride(1) == width and rows that do not overlap; the
         head counts and widths agree; no output shares storage with an input, another output or ``work``; all live on one GPU.
-        ``dt``: the dtype the operands must have instead of the handle's (``mhaLowp``: Q's).  Returns (heads, k, d)."""
+        ``dt``: the dtype the operands must have instead of the handle's (``mhaLowp``: Q's); ``work_dt``: the dtype ``work`` must
+        have instead of the operands' (``mhaLowpBackward``: float32).  Returns (heads, k, d)."""
         holds = "the handle holds" if dt is None else "Q has"
         dt = dt or ("torch.float64" if self._vt == _capi.F64 else "torch.float32")
         for name, t, rows, width in ins + outs:
@@ -338,7 +339,9 @@ class anonymouslibHandle:
         if work is not None or any(name in ("dK", "dV") for name, _, _, _ in outs):
             if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
                 raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
-            if str(work.dtype) != dt:
+            if work_dt is not None and str(work.dtype) != work_dt:
+                raise ValueError(f"{who}: work has dtype {work.dtype}, it must be {work_dt} whatever the operands' dtype")
+            if work_dt is None and str(work.dtype) != dt:
                 raise ValueError(f"{who}: work has dtype {work.dtype}, the handle holds {dt}")
             if work.dim() != 1 or work.shape[0] < 4 * self._m * heads:
                 raise ValueError(f"{who}: work must have shape ({4 * self._m * heads},) or longer, not {tuple(work.shape)}")
@@ -573,7 +576,7 @@ class anonymouslibHandle:
                                                         _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
                                                         _ptr(dB), int(lddb))
 
-    # -- the forward with operands stored in bf16 / fp16, computed in fp32 (csr5hip_lowp.h csr5hip_mha_lowp) -------
+    # -- the same with operands stored in bf16 / fp16, computed in fp32 (csr5hip_lowp.h csr5hip_mha_lowp and its backward) -------
     _LOWP = {"torch.bfloat16": _capi.BF16, "torch.float16": _capi.F16}
 
     def mhaLowp(self, Q, K, V, O, B=None, scale=1.0) -> int:
@@ -603,6 +606,45 @@ class anonymouslibHandle:
         dimensions in elements of that type; B None for no bias"""
         return self._lib.csr5hip_mha_lowp(self._h, int(operand_type), int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq),
                                           _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo))
+
+    def mhaLowpBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None, B=None, scale=1.0, dB=None) -> int:
+        """the gradients of ``mhaLowp`` in TWO launches, ``mhaEdgeBiasBackward`` on operands STORED IN 16 BITS: Q, K, V, dO, B
+        (when given) and the wanted outputs dQ, dK, dV, dB are all ``torch.bfloat16`` or all ``torch.float16``, WHATEVER THE
+        HANDLE'S DTYPE.  Everything is computed in fp32 and each output is rounded once where it is stored, so each is, bit for bit
+        (NaN payloads apart), what ``mhaEdgeBiasBackward`` on an fp32 handle writes for the widened operands, cast to the operand
+        type.  ``work`` is a contiguous 1-D ``torch.float32`` tensor of at least 4 m H values, whatever the operands' and the
+        handle's dtype: it carries the row maxima, 1 / Z and D unrounded from the row kernel to the column kernel.  dK and dV need
+        ``work`` and the transposed companion (``buildTranspose``; it is never built here), dB and dQ neither.  Layouts, strides,
+        devices and aliasing as ``mhaEdgeBiasBackward``.  The handle's values are not read.  Anything else raises ValueError
+        before the library is called."""
+        who = "mhaLowpBackward"
+        ot = self._LOWP.get(str(getattr(Q, "dtype", None)))
+        if ot is None:
+            raise ValueError(f"{who}: Q must be a torch.bfloat16 or torch.float16 tensor, not {getattr(Q, 'dtype', type(Q).__name__)}")
+        dt = str(Q.dtype)
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
+        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others, dt)
+        heads, k, d = self._mha_args(who, ins, outs, work, dt, "torch.float32")
+        if B is not None:
+            for oname, o, _, _ in outs:
+                if o.numel() and B.numel() and o.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
+                    raise ValueError(f"{who}: {oname} shares storage with B (aliased)")
+        self._mha_edge_device(who, Q, (("B", B), ("dB", dB)))
+        ld = self._mha_ld
+        return self.mha_lowp_backward_ptr(ot, heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
+                                          ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k,
+                                          dV, ld(dV) if dV is not None else heads * d, work, dB, lddb)
+
+    def mha_lowp_backward_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
+                              ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int) -> int:
+        """csr5hip_mha_lowp_backward on raw device pointers (or tensors): operand_type ``_capi.BF16`` or ``_capi.F16``, the leading
+        dimensions in elements of that type, work float; None for B or for an output that is not wanted"""
+        return self._lib.csr5hip_mha_lowp_backward(self._h, int(operand_type), int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q),
+                                                   int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO), int(lddo),
+                                                   _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work), _ptr(dB),
+                                                   int(lddb))
 
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:

@@ -229,7 +229,18 @@ public:
     {
         return _h ? csr5hip_mha_lowp(_h, operand_type, heads, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, d, O, ldo) : _err;
     }
-    // extension: its gradients in two launches, operands as mhaBackward; dB (or null): nnz x heads values, the gradient of B, entry e
+    // extension: mhaLowp's gradients in two launches -- B, Q, K, V, dO and the outputs dQ, dK, dV, dB device pointers to operand_type,
+    // leading dimensions in its elements; work: 4 m heads FLOAT values whatever ANONYMOUSLIB_VT is; every output rounded once
+    // (csr5hip_mha_lowp_backward)
+    int mhaLowpBackward(int operand_type, int heads, double scale, const void *B, int ldb, const void *Q, int ldq, const void *K, int ldk,
+                        int k, const void *V, int ldv, int d, const void *dO, int lddo, void *dQ, int lddq, void *dK, int lddk, void *dV,
+                        int lddv, void *work, void *dB, int lddb)
+    {
+        return _h ? csr5hip_mha_lowp_backward(_h, operand_type, heads, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, d, dO, lddo, dQ, lddq,
+                                              dK, lddk, dV, lddv, work, dB, lddb)
+                  : _err;
+    }
+    // extension: mhaEdgeBias's gradients in two launches, operands as mhaBackward; dB (or null): nnz x heads values, the gradient of B, entry e
     // and head h at dB[e lddb + h] (csr5hip_mha_edge_bias_backward)
     int mhaEdgeBiasBackward(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,
                             const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,

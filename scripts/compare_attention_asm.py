@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Do the existing attention kernels still have the code they had?  Cross-compiles csr5_attention.hip, csr5_attention_bwd.hip, the
 two biased units (csr5_attention_bias.hip, csr5_attention_bwd_bias.hip), the two edge-biased ones (csr5_attention_edge.hip,
-csr5_attention_bwd_edge.hip) and the 16-bit one (csr5_attention_lowp.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
+csr5_attention_bwd_edge.hip) and the 16-bit ones (csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
 -S, once per value or operand type) from a git revision and from the working tree, and compares every kernel of the revision
-(k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>, k_attention_edge<..>, k_attention_bwd_edge<..>, k_attention_lowp<..>) with the kernel of the same symbol
+(k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>, k_attention_edge<..>, k_attention_bwd_edge<..>, k_attention_lowp<..>, k_attention_bwd_lowp<..>) with the kernel of the same symbol
 now, instruction for instruction and register for register.  No GPU needed.
 
     python scripts/compare_attention_asm.py [--rev HEAD~1] [--keep DIR]
@@ -29,7 +29,8 @@ UNITS = (("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention.hip
          ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_bias.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
          ("csr5_attention_edge.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_edge.hip", "CSR5_ATTENTION_ONLY_F32"),
          ("csr5_attention_bwd_edge.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_edge.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
-         ("csr5_attention_lowp.hip", "CSR5_LOWP_ONLY_BF16"), ("csr5_attention_lowp.hip", "CSR5_LOWP_ONLY_F16"))
+         ("csr5_attention_lowp.hip", "CSR5_LOWP_ONLY_BF16"), ("csr5_attention_lowp.hip", "CSR5_LOWP_ONLY_F16"),
+         ("csr5_attention_bwd_lowp.hip", "CSR5_LOWP_ONLY_BF16"), ("csr5_attention_bwd_lowp.hip", "CSR5_LOWP_ONLY_F16"))
 
 
 def kernels(tree, src, define, out):
@@ -64,6 +65,9 @@ def main():
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
         bad = total = 0
         for src, define in UNITS:
+            if not os.path.exists(os.path.join(old, CSRC, src)):  # (a unit the revision does not have yet: nothing to compare)
+                print(f"new unit  {src} ({define}): not in {args.rev}")
+                continue
             tag = f"{os.path.splitext(src)[0]}_{define.rsplit('_', 1)[1].lower()}"  # (.._f64, .._f32, .._bf16, .._f16)
             was = kernels(old, src, define, os.path.join(work, f"rev_{tag}.s"))
             now = kernels(ROOT, src, define, os.path.join(work, f"tree_{tag}.s"))
