@@ -226,6 +226,19 @@ SYMBOLS_LOWP_BACKWARD = [
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
 ]
 
+# the additive (GAT, GATv2) attention calls, bound by load() like the others: heads, negative_slope (double), a, then
+# csr5hip_mha_edge_bias's / csr5hip_mha_edge_bias_backward's arguments from the scale on, the backward's followed by dAr and lddar.  A
+# list of their own for SYMBOLS_BIASED's reason: their declarations are in include/csr5hip_gat.h; tests/test_gat_host.py compares them
+# with the exports.
+SYMBOLS_GAT = [
+    ("csr5hip_gat", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                              C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("csr5hip_gat_backward", C.c_int, [_H, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int]),
+]
+
 _lib = None
 
 
@@ -248,7 +261,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -52,7 +52,7 @@ import torch
 
 from . import _capi
 
-__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention"]
+__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention", "gat_attention"]
 
 
 def _check(rc: int, what: str) -> None:
@@ -517,3 +517,66 @@ def multihead_attention(A, Q, K, V, scale=None, bias=None, slopes=None):
     if slopes is not None and bias is None and slopes.requires_grad and torch.is_grad_enabled():
         raise ValueError("multihead_attention: slopes needs a gradient, which is formed from the bias: give bias as a tensor")
     return _BiasedMultiheadAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias, slopes)
+
+
+class _GatAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V, att, negative_slope, scale, bias):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        ac = att.detach().contiguous() if att is not None else None
+        Bc = _rows_packed(bias.detach()) if bias is not None else None
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.gat(Qc, Kc, Vc, O, a=ac, negative_slope=negative_slope, B=Bc, scale=scale), "gat")
+        ctx.A, ctx.ns, ctx.scale = A, negative_slope, scale
+        ctx.save_for_backward(Qc, Kc, Vc, ac, Bc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, a, B = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        need_att = a is not None and ctx.needs_input_grad[4]
+        need_bias = B is not None and ctx.needs_input_grad[7]
+        if not (any(need) or need_att or need_bias):
+            return (None,) * 8
+        A = ctx.A
+        dO = _packed(dO.detach())
+        _on_current_stream(A, dO.device)
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
+        work = None
+        if need[1] or need[2]:
+            if not A.info().transpose_built:
+                _check(A.buildTranspose(), "buildTranspose")
+            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        dAr = torch.empty_like(Q, memory_format=torch.contiguous_format) if need_att else None  # (every row and head is written)
+        _check(A.gatBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, a=a, negative_slope=ctx.ns, B=B, scale=ctx.scale, dB=dB,
+                             dAr=dAr), "gatBackward")
+        grad_att = dAr.sum(0) if need_att else None  # (the kernels write the rows' shares: the reduction over the rows is torch's)
+        return (None,) + tuple(outs) + (grad_att, None, None, dB)
+
+
+def gat_attention(A, Q, K, V, att=None, negative_slope=0.2, scale=None, bias=None):
+    """additive attention on the pattern, differentiable: packed Q (m, H, k), K (n, H, k), V (n, H, d) -> (m, H, d) with the weights
+    ``softmax(scale * sum_c att[h, c] LeakyReLU(Q[i, h, c] + K[j, h, c]) + bias[e, h])`` over the stored entries of row i.
+
+    * GAT:   k = 1, ``att=None``, Q = el, K = er (the two halves of the attention vector applied to the features): the score is
+             ``LeakyReLU(el[i, h] + er[j, h])``.
+    * GATv2: k = the feature width, Q = W_l x, K = W_r x, ``att`` the (H, k) attention vector; ``K`` and ``V`` may be the same
+             tensor (autograd adds their two gradients).
+
+    ``negative_slope`` is the LeakyReLU's, ``scale`` a Python float (``None`` for 1.0), neither differentiable; ``bias`` ``None`` or
+    a 2-D (nnz, H) tensor in CSR order as ``multihead_attention``'s per-head edge bias, differentiable.  The non-linearity sits
+    INSIDE the score, so no choice of Q, K and bias turns ``multihead_attention`` into this.
+
+    Forward is ONE ``A.gat`` (one launch) into ``torch.empty`` on torch's current stream; Q, K, V, att and bias are kept.  Backward
+    is ONE ``A.gatBackward`` (two launches): ``torch.empty`` outputs for exactly what needs a gradient, a workspace of 4 m H
+    values and the transposed companion (``buildTranspose``, once per conversion) only when K or V needs one.  ``grad_att`` is
+    ``dAr.sum(0)`` of the (m, H, k) per-row shares the row kernel writes, allocated only when ``att`` needs a gradient;
+    ``grad_bias`` IS the dB the kernel writes, allocated only when the bias needs one.  Otherwise nothing of length nnz is
+    allocated; the handle is given no values and its values are not read.  Nothing runs in backward when nothing needs a
+    gradient.  fp32 and fp64 handles; there is no 16-bit route."""
+    if bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2):
+        raise ValueError("gat_attention: bias is None or a 2-D (nnz, H) tensor in CSR order")
+    return _GatAttention.apply(A, Q, K, V, att, float(negative_slope), 1.0 if scale is None else float(scale), bias)

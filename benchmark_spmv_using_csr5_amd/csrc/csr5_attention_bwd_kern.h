@@ -19,6 +19,7 @@ template <typename VT>
 struct AttBwdArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's rank in the parent's CSR order)
+    static constexpr bool GAT = false;  // (with EDGE: the additive score of AttBwdGatArgs in place of the dot product)
     using ST = VT;                      // the type behind the operand and output pointers (AttBwdLowpArgs: another one than VT)
     int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
@@ -59,6 +60,19 @@ struct AttBwdEdgeArgs : AttBwdArgs<VT> {
     int ldds;
 };
 
+// csr5hip_gat_backward (csr5_attention_bwd_gat.hip): the edge call with s = fma(z, c, B[e, h]), z the additive score's chain
+// (att_gat_z).  p, dp, D, ds, t, dV and dS / dB are the edge call's with these scores.  u_c = Q[i, c] + K[j, c] and l_c are recomputed
+// where they are needed, the forward's bits on both sides; the accumulations take the operand w_c = a_c g_c, g_c = u_c > 0 ? 1 : ns,
+// in K's / Q's place (gat_short_acc, gat_wave_acc, gat_hub_acc), and the row kernel accumulates t_e l_ec next to t_e w_ec into
+// dAr[i * lddar + h k + c], the row's share of a's gradient (null: not wanted).
+template <typename VT>
+struct AttBwdGatArgs : AttBwdEdgeArgs<VT> {
+    static constexpr bool GAT = true;
+    AttGat<VT> gat;
+    VT *dAr;
+    int lddar;
+};
+
 // csr5hip_mha_lowp_backward (csr5_attention_bwd_lowp.hip): AttBwdEdgeArgs<float>'s call with Q, K, V, B and dO STORED in ST (bf16 or
 // fp16) and dQ, dK, dV and dB written in it.  The arithmetic, the LDS stage, the reductions and the workspace are float: the templates
 // below widen an operand where they load it and round an output once where they store it (att_stored), and are otherwise the float
@@ -67,6 +81,7 @@ template <typename ST_>
 struct AttBwdLowpArgs {
     static constexpr bool BIASED = true;
     static constexpr bool EDGE = true;
+    static constexpr bool GAT = false;
     using ST = ST_;
     int lines, k, d;
     int T, sigma, tiles;
@@ -104,6 +119,12 @@ __device__ __forceinline__ ARGS bwd_head(const ARGS &A, const int h)
         H.dV += od;
     if (H.work)
         H.work += 4 * (size_t)h;
+    if constexpr (ARGS::GAT) {
+        if (H.gat.a)
+            H.gat.a += ok;
+        if (H.dAr)
+            H.dAr += ok;
+    }
     if constexpr (ARGS::EDGE) {
         if (H.bias.B)
             H.bias.B += h;
@@ -155,11 +176,15 @@ __device__ __forceinline__ void bwd_store_ds(const ARGS &A, const int t0, const 
 template <typename VT, bool VEC, typename ARGS>
 __device__ __forceinline__ VT bwd_score(const ARGS &A, const size_t i, const size_t j, const VT av)
 {
-    const VT s = att_score<VT, VEC>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
-    if constexpr (ARGS::BIASED)
-        return att_bias_score(A.bias, 0, s, av);
-    else
-        return s;
+    if constexpr (ARGS::GAT) {
+        return att_bias_score(A.bias, 0, att_gat_z<VT>(A.Q + i * A.ldq, A.K + j * A.ldk, A.gat.a, A.gat.ns, A.k), av);
+    } else {
+        const VT s = att_score<VT, VEC>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
+        if constexpr (ARGS::BIASED)
+            return att_bias_score(A.bias, 0, s, av);
+        else
+            return s;
+    }
 }
 
 // s_e and dp_e of the entry (i, j); av: its value (read only when biased)
@@ -288,6 +313,163 @@ __device__ __forceinline__ void bwd_hub_acc(const int rl, const bool staged, FIL
     __syncthreads();
 }
 
+// ---- the additive score's accumulations (ARGS::GAT): bwd_short_acc, bwd_wave_acc and bwd_hub_acc with the operand of entry e and
+// column c computed instead of loaded: u = Q's element + K's (X[idx[e]] holds one of them, self -- the line's own row of Q in the
+// row kernel, of K in the column kernel -- the other; Q's first, as the forward adds them), g = u > 0 ? 1 : ns, w = a_c * g (one
+// rounding; a null: w = g), acc = fma(coef_e, w, acc).  The orders are those routines', so dQ and dK keep mha_backward's accumulation
+// rules.  SECOND (the row kernel): a second chain acc2 = fma(coef_e, l, acc2), l = LeakyReLU(u), in the same order, written to out2.
+// out / out2: null when not wanted (at least one is).
+template <typename VT, bool COL>
+__device__ __forceinline__ VT gat_u(const VT x, const VT self)
+{
+    return COL ? x + self : self + x;
+}
+
+template <typename VT, bool COL, bool SECOND>
+__device__ __forceinline__ void gat_short_acc(const bool rowok, const int rl, const int sub, const int pos, const VT coef, const int idx,
+                                              const VT *__restrict__ X, const int ldx, const VT *__restrict__ self,
+                                              const VT *__restrict__ av, const VT ns, const int width, VT *out, VT *out2)
+{
+    constexpr int G = AT_G;
+    for (int cb = 0; cb < width; cb += G) { // (uniform)
+        const int c = cb + pos;
+        VT acc = (VT)0, acc2 = (VT)0, y = (VT)0, ac = (VT)1;
+        if (rowok && c < width) {
+            y = self[c];
+            if (av)
+                ac = av[c];
+        }
+        for (int e = 0; e < G; e++) {
+            if (!__any(rowok && e < rl)) // (uniform: the shuffles below are executed by every lane)
+                break;
+            const VT we = __shfl(coef, sub * G + e, OMEGA);
+            const int je = __shfl(idx, sub * G + e, OMEGA);
+            if (rowok && e < rl && c < width) {
+                const VT u = gat_u<VT, COL>(X[(size_t)(uint32_t)je * ldx + c], y);
+                const VT g = u > (VT)0 ? (VT)1 : ns;
+                acc = fma_vt(we, av ? ac * g : g, acc);
+                if constexpr (SECOND)
+                    acc2 = fma_vt(we, att_gat_leaky(u, ns), acc2);
+            }
+        }
+        if (rowok && c < width) {
+            if (out)
+                out[c] = acc;
+            if constexpr (SECOND)
+                if (out2)
+                    out2[c] = acc2;
+        }
+    }
+}
+
+template <typename VT, bool COL, bool SECOND>
+__device__ __forceinline__ void gat_wave_acc(const VT *coef, const int *idx, const int rl, const VT *__restrict__ X, const int ldx,
+                                             const VT *__restrict__ self, const VT *__restrict__ av, const VT ns, const int width,
+                                             VT *out, VT *out2)
+{
+    const int lane = threadIdx.x & (OMEGA - 1);
+    for (int cb = 0; cb < width; cb += OMEGA) {
+        const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+        const int C = att_pow2(wb), S = OMEGA / C;
+        const int slot = lane / C, cc = lane & (C - 1);
+        VT acc = (VT)0, acc2 = (VT)0;
+        if (cc < wb) {
+            const VT *x = X + cb + cc;
+            const VT y = self[cb + cc];
+            const VT ac = av ? av[cb + cc] : (VT)1;
+#pragma unroll 4
+            for (int e = slot; e < rl; e += S) {
+                const VT u = gat_u<VT, COL>(x[(size_t)(uint32_t)idx[e] * ldx], y);
+                const VT g = u > (VT)0 ? (VT)1 : ns;
+                acc = fma_vt(coef[e], av ? ac * g : g, acc);
+                if constexpr (SECOND)
+                    acc2 = fma_vt(coef[e], att_gat_leaky(u, ns), acc2);
+            }
+        }
+        for (int off = C; off < OMEGA; off <<= 1) { // (uniform; adjacent slots first)
+            acc += __shfl_xor(acc, off, OMEGA);
+            if constexpr (SECOND)
+                acc2 += __shfl_xor(acc2, off, OMEGA);
+        }
+        if (slot == 0 && cc < wb) {
+            if (out)
+                out[cb + cc] = acc;
+            if constexpr (SECOND)
+                if (out2)
+                    out2[cb + cc] = acc2;
+        }
+    }
+}
+
+template <typename VT, bool COL, bool SECOND, typename FILL>
+__device__ __forceinline__ void gat_hub_acc(const int rl, const bool staged, FILL fill, const VT *coef, const int *idx,
+                                            const VT *__restrict__ X, const int ldx, const VT *__restrict__ self,
+                                            const VT *__restrict__ av, const VT ns, const int width, VT *out, VT *out2, VT *red)
+{
+    const int tid = (int)threadIdx.x;
+    for (int cg = 0; cg < width; cg += OMEGA * AT_HUB_BLOCKS) {
+        VT acc[AT_HUB_BLOCKS], acc2[AT_HUB_BLOCKS];
+#pragma unroll
+        for (int b = 0; b < AT_HUB_BLOCKS; b++) {
+            acc[b] = (VT)0;
+            acc2[b] = (VT)0;
+        }
+        for (int base = 0; base < rl; base += AT_STAGE) {
+            const int n = rl - base < AT_STAGE ? rl - base : AT_STAGE;
+            if (!staged) {
+                __syncthreads(); // (the stage is free: the previous chunk has been read)
+                fill(base, n);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int b = 0; b < AT_HUB_BLOCKS; b++) {
+                const int cb = cg + b * OMEGA;
+                if (cb < width) {
+                    const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+                    const int C = att_pow2(wb), S = AT_BLOCK / C; // (AT_STAGE is a multiple of S: a chunk keeps j mod S)
+                    const int slot = tid / C, cc = tid & (C - 1);
+                    if (cc < wb) {
+                        const VT *x = X + cb + cc;
+                        const VT y = self[cb + cc];
+                        const VT ac = av ? av[cb + cc] : (VT)1;
+                        VT o = acc[b], o2 = acc2[b];
+#pragma unroll 4
+                        for (int e = slot; e < n; e += S) {
+                            const VT u = gat_u<VT, COL>(x[(size_t)(uint32_t)idx[e] * ldx], y);
+                            const VT g = u > (VT)0 ? (VT)1 : ns;
+                            o = fma_vt(coef[e], av ? ac * g : g, o);
+                            if constexpr (SECOND)
+                                o2 = fma_vt(coef[e], att_gat_leaky(u, ns), o2);
+                        }
+                        acc[b] = o;
+                        acc2[b] = o2;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < AT_HUB_BLOCKS; b++) {
+            const int cb = cg + b * OMEGA;
+            if (cb < width) { // (uniform)
+                const int wb = width - cb < OMEGA ? width - cb : OMEGA;
+                const int C = att_pow2(wb);
+                for (int second = 0; second < (SECOND ? 2 : 1); second++) { // (uniform)
+                    VT o = second ? acc2[b] : acc[b];
+                    VT *dst = second ? out2 : out;
+                    for (int off = C; off < OMEGA; off <<= 1) // adjacent slots of the wavefront first ...
+                        o += __shfl_xor(o, off, OMEGA);
+                    red[tid] = o;
+                    __syncthreads();
+                    if (tid < wb && dst) // ... then (w0 + w1) + (w2 + w3); lane c < C of every wavefront holds column c
+                        dst[cb + tid] = (red[tid] + red[OMEGA + tid]) + (red[2 * OMEGA + tid] + red[3 * OMEGA + tid]);
+                    __syncthreads(); // (red is free for the next block)
+                }
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // ---- lines of at most 16 entries (empty ones included): 16 lanes per line, 4 lines of the wavefront per pass ---------------
 template <typename VT, bool VEC, bool COL, typename ARGS>
 __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, const int len, const int t0, const int rem0,
@@ -333,7 +515,11 @@ __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, 
                     bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, av, p, ds);
                 if (A.dV)
                     bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
-                if (A.dK)
+                if constexpr (ARGS::GAT) {
+                    if (A.dK)
+                        gat_short_acc<VT, true, false>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.K + r * A.ldk, A.gat.a, A.gat.ns,
+                                                       A.k, A.dK + r * A.lddk, nullptr);
+                } else if (A.dK)
                     bwd_short_acc<VT>(rowok, rl, sub, pos, ds, other, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
             } else {
                 VT s = neg_inf<VT>(), dp = (VT)0;
@@ -354,7 +540,12 @@ __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, 
                 }
                 if (act)
                     bwd_store_ds(A, rt0, rrem, pos, ds);
-                if (A.dQ)
+                if constexpr (ARGS::GAT) {
+                    if (A.dQ || A.dAr)
+                        gat_short_acc<VT, false, true>(rowok, rl, sub, pos, bwd_coef(A, ds), other, A.K, A.ldk, A.Q + r * A.ldq,
+                                                       A.gat.a, A.gat.ns, A.k, A.dQ ? A.dQ + r * A.lddq : nullptr,
+                                                       A.dAr ? A.dAr + r * A.lddar : nullptr);
+                } else if (A.dQ)
                     bwd_short_acc<VT>(rowok, rl, sub, pos, bwd_coef(A, ds), other, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
             }
         }
@@ -381,7 +572,11 @@ __device__ __forceinline__ void bwd_wave_head(const ARGS &A, const bool first, c
         att_wave_sync();
         if (A.dV)
             bwd_wave_acc<VT>(a, cl, rl, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
-        if (A.dK)
+        if constexpr (ARGS::GAT) {
+            if (A.dK)
+                gat_wave_acc<VT, true, false>(b, cl, rl, A.Q, A.ldq, A.K + r * A.ldk, A.gat.a, A.gat.ns, A.k, A.dK + r * A.lddk,
+                                              nullptr);
+        } else if (A.dK)
             bwd_wave_acc<VT>(b, cl, rl, A.Q, A.ldq, A.k, A.dK + r * A.lddk);
     } else {
         VT mx = neg_inf<VT>();
@@ -423,7 +618,11 @@ __device__ __forceinline__ void bwd_wave_head(const ARGS &A, const bool first, c
             wk[2] = D;
         }
         att_wave_sync();
-        if (A.dQ)
+        if constexpr (ARGS::GAT) {
+            if (A.dQ || A.dAr)
+                gat_wave_acc<VT, false, true>(a, cl, rl, A.K, A.ldk, A.Q + r * A.ldq, A.gat.a, A.gat.ns, A.k,
+                                              A.dQ ? A.dQ + r * A.lddq : nullptr, A.dAr ? A.dAr + r * A.lddar : nullptr);
+        } else if (A.dQ)
             bwd_wave_acc<VT>(a, cl, rl, A.K, A.ldk, A.k, A.dQ + r * A.lddq);
     }
     att_wave_sync(); // (the next head's and the next line's entries stay behind these reads)
@@ -462,7 +661,11 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
             fill(0, rl);
         if (A.dV)
             bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.dO, A.lddo, A.d, A.dV + r * A.lddv, red);
-        if (A.dK)
+        if constexpr (ARGS::GAT) {
+            if (A.dK)
+                gat_hub_acc<VT, true, false>(rl, staged, fill, b, cl, A.Q, A.ldq, A.K + r * A.ldk, A.gat.a, A.gat.ns, A.k,
+                                             A.dK + r * A.lddk, nullptr, red);
+        } else if (A.dK)
             bwd_hub_acc<VT>(rl, staged, fill, b, cl, A.Q, A.ldq, A.k, A.dK + r * A.lddk, red);
     } else {
         VT mx = neg_inf<VT>();
@@ -549,7 +752,13 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
                 cl[jj] = cj;
             }
         };
-        if (A.dQ)
+        if constexpr (ARGS::GAT) {
+            if (A.dQ || A.dAr)
+                gat_hub_acc<VT, false, true>(rl, staged, fill, a, cl, A.K, A.ldk, A.Q + r * A.ldq, A.gat.a, A.gat.ns, A.k,
+                                             A.dQ ? A.dQ + r * A.lddq : nullptr, A.dAr ? A.dAr + r * A.lddar : nullptr, red);
+            else
+                __syncthreads();
+        } else if (A.dQ)
             bwd_hub_acc<VT>(rl, staged, fill, a, cl, A.K, A.ldk, A.k, A.dQ + r * A.lddq, red);
         else
             __syncthreads(); // (the stage is free for the next head or hub line)
@@ -639,6 +848,13 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_edge(const AttBwdEdg
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }
 
+// the additive score likewise.  VEC: the dp chain's 16-byte loads of dO and V; the score takes element loads
+template <typename VT, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_gat(const AttBwdGatArgs<VT> A)
+{
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+
 // 16-bit operands and outputs, float arithmetic: always the packed, edge-biased call.  6 waves per SIMD are
 // k_attention_bwd_edge<float, ..>'s: left to itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 81
 // (row kernel) and 82 (column kernel) registers with 16-byte loads, which are 5 waves
@@ -669,6 +885,11 @@ template <bool VEC, bool COL, bool MH, typename VT>
 static void attention_bwd_enqueue(const AttBwdEdgeArgs<VT> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_bwd_edge<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdGatArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_gat<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 
 template <bool VEC, bool COL, bool MH, typename ST>
@@ -717,7 +938,11 @@ static hipError_t attention_bwd_side(const Geometry &g, const DeviceArrays &d, A
     attention_bwd_fill(A, g, d, c.groups);
     if constexpr (ARGS::BIASED)
         att_set_bias(A.bias, d, map, c);
-    const bool vec = attention_bwd_vec<typename ARGS::ST>(c.heads, c.k, c.d, c.Q, c.ldq, c.K, c.ldk, c.V, c.ldv, c.dO, c.lddo);
+    bool vec;
+    if constexpr (ARGS::GAT) // (only the dp chain over dO and V takes 16-byte loads: Q and K need no alignment)
+        vec = attention_bwd_vec<typename ARGS::ST>(c.heads, 0, c.d, c.V, c.ldv, c.V, c.ldv, c.V, c.ldv, c.dO, c.lddo);
+    else
+        vec = attention_bwd_vec<typename ARGS::ST>(c.heads, c.k, c.d, c.Q, c.ldq, c.K, c.ldk, c.V, c.ldv, c.dO, c.lddo);
     const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
     if (A.heads == 1) {
         const dim3 grid(blocks);
@@ -763,9 +988,14 @@ hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const 
     void *dS = nullptr;
     if constexpr (ARGS::BIASED)
         dS = c.dS;
+    void *dAr = nullptr; // (the additive score's second row-side output: wanted as dQ is)
+    if constexpr (ARGS::GAT) {
+        att_set_gat(A.gat, c);
+        dAr = c.k > 0 ? c.dAr : nullptr;
+    }
     const bool column = c.gt && c.dt && (!ARGS::EDGE || c.map) && (c.dK || c.dV);
     hipError_t e = hipSuccess;
-    if (c.dQ || dS || column) {
+    if (c.dQ || dS || column || dAr) {
         ARGS R = A;
         R.dQ = c.k > 0 ? (ST *)c.dQ : nullptr;
         R.work = column ? (VT *)c.work : nullptr;
@@ -773,7 +1003,11 @@ hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const 
             R.dS = (ST *)dS;
             R.ldds = c.ldds;
         }
-        if (R.dQ || R.work || dS)
+        if constexpr (ARGS::GAT) {
+            R.dAr = (ST *)dAr;
+            R.lddar = c.lddar;
+        }
+        if (R.dQ || R.work || dS || dAr)
             e = attention_bwd_side<false, VT>(g, d, R, nullptr, c, s);
     }
     if (e == hipSuccess && column) {

@@ -205,6 +205,48 @@ __device__ __forceinline__ float att_bias_score(const AttEdgeBiasLowpMap<ST> &E,
     return fma_vt(qk, E.c, b);
 }
 
+// The additive score of csr5hip_gat and its backward (csr5_attention_gat.hip): the attention vector, head h's k values at a[h * k],
+// or null (a = 1), and the negative slope of the LeakyReLU, converted once to the value type.  It rides NEXT TO an AttEdgeBias: the
+// scale, B and the map are the edge call's.
+template <typename VT>
+struct AttGat {
+    const VT *a;
+    VT ns;
+};
+
+// u and l of one channel: u = q + k (one rounded addition, Q's element first on both sides of the backward), l = LeakyReLU(u)
+template <typename VT>
+__device__ __forceinline__ VT att_gat_leaky(const VT u, const VT ns)
+{
+    return u > (VT)0 ? u : ns * u;
+}
+
+// the chain of the definition over one row of Q and one of K: z = fma(a_c, l_c, z), c = 0, 1, 2, ..., from +0; a: that head's k
+// values, or null (a = 1: fma(1, l, z) has the bits of z + l).  Element loads only: a 16-byte block would feed one addition each
+template <typename VT>
+__device__ __forceinline__ VT att_gat_z(const VT *__restrict__ q, const VT *__restrict__ kr, const VT *__restrict__ a, const VT ns,
+                                        const int k)
+{
+    VT z = (VT)0;
+    if (a) {
+#pragma unroll 4
+        for (int c = 0; c < k; c++)
+            z = fma_vt(a[c], att_gat_leaky(q[c] + kr[c], ns), z);
+    } else {
+#pragma unroll 4
+        for (int c = 0; c < k; c++)
+            z = fma_vt((VT)1, att_gat_leaky(q[c] + kr[c], ns), z);
+    }
+    return z;
+}
+
+template <typename VT>
+static void att_set_gat(AttGat<VT> &g, const AttCall &c)
+{
+    g.a = (const VT *)c.a;
+    g.ns = (VT)c.negative_slope;
+}
+
 // The variant-specific part of a launch, forward and backward alike: the bias fields from the call.  side: the arrays of the pattern
 // the kernel walks (the parent's, or the companion's in the column kernel); map: null where that pattern is the parent's, the
 // companion's source map in the column kernel.

@@ -20,6 +20,7 @@ template <typename VT>
 struct AttArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's CSR rank)
+    static constexpr bool GAT = false;  // (with EDGE: the additive score of AttGatArgs in place of the dot product)
     using ST = VT;                      // the type Q, K, V and O are stored in (AttLowpArgs: another one than the arithmetic's)
     int m, k, d;
     int heads, hper;     // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
@@ -48,6 +49,21 @@ struct AttEdgeArgs : AttArgs<VT> {
     AttEdgeBias<VT> bias;
 };
 
+// csr5hip_gat (csr5_attention_gat.hip): the edge call with z = sum_c a[h, c] LeakyReLU(Q[i, h, c] + K[j, h, c]) (att_gat_z) in the
+// dot product's place: s = fma(z, c, B[e * ldb + h]).  Everything after the score is the edge call's
+template <typename VT>
+struct AttGatArgs : AttEdgeArgs<VT> {
+    static constexpr bool GAT = true;
+    AttGat<VT> gat;
+};
+
+// the additive score's z of an entry of head h: att_gat_z on that head's k values of a
+template <typename VT, typename ARGS>
+__device__ __forceinline__ VT att_gat_chain(const ARGS &A, const int h, const VT *q, const VT *kr)
+{
+    return att_gat_z<VT>(q, kr, A.gat.a ? A.gat.a + (size_t)h * A.k : nullptr, A.gat.ns, A.k);
+}
+
 // csr5hip_mha_lowp (csr5_attention_lowp.hip): AttEdgeArgs<float>'s call with Q, K, V, B and O STORED in ST (bf16 or fp16).  The
 // arithmetic is float: the templates below widen an operand where they load it and round once where they store O, and are
 // otherwise the float instantiation's, statement for statement -- the result is the rounding of the float call's on the widened
@@ -56,6 +72,7 @@ template <typename ST_>
 struct AttLowpArgs {
     static constexpr bool BIASED = true;
     static constexpr bool EDGE = true;
+    static constexpr bool GAT = false;
     using ST = ST_;
     int m, k, d;
     int heads, hper;
@@ -108,7 +125,12 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
             typename ARGS::ST *Oh = A.O + (size_t)h * A.d;
             VT s = neg_inf<VT>();
             if (act) {
-                s = att_score<VT, VEC>(A.Q + r * A.ldq + (size_t)h * A.k, A.K + (size_t)(uint32_t)cj * A.ldk + (size_t)h * A.k, A.k);
+                if constexpr (ARGS::GAT)
+                    s = att_gat_chain<VT>(A, h, A.Q + r * A.ldq + (size_t)h * A.k,
+                                          A.K + (size_t)(uint32_t)cj * A.ldk + (size_t)h * A.k);
+                else
+                    s = att_score<VT, VEC>(A.Q + r * A.ldq + (size_t)h * A.k, A.K + (size_t)(uint32_t)cj * A.ldk + (size_t)h * A.k,
+                                           A.k);
                 if constexpr (ARGS::EDGE)
                     s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, er, h));
                 else if constexpr (ARGS::BIASED)
@@ -153,7 +175,11 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
             } else {
                 cj = cl[j];
             }
-            VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
+            VT s;
+            if constexpr (ARGS::GAT)
+                s = att_gat_chain<VT>(A, h, q, Kh + (size_t)(uint32_t)cj * A.ldk);
+            else
+                s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
             if constexpr (ARGS::EDGE) // (the bias is read from the entry's rank by every head: it is not staged either)
                 s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h));
             else if constexpr (ARGS::BIASED) // (the value is read again from the column's index by every head: it is not staged)
@@ -208,7 +234,11 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const t
             cj = A.col[att_storage(A, t0, rem0, j)];
         else
             cj = cl[j];
-        VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
+        VT s;
+        if constexpr (ARGS::GAT)
+            s = att_gat_chain<VT>(A, h, q, Kh + (size_t)(uint32_t)cj * A.ldk);
+        else
+            s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
         if constexpr (ARGS::EDGE)
             s = att_bias_score(A.bias, h, s, att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h));
         else if constexpr (ARGS::BIASED)
@@ -242,7 +272,11 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const t
                 for (int jj = tid; jj < n; jj += AT_BLOCK) {
                     const size_t st = att_storage(A, t0, rem0, base + jj);
                     const int cj = A.col[st];
-                    VT s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
+                    VT s;
+                    if constexpr (ARGS::GAT)
+                        s = att_gat_chain<VT>(A, h, q, Kh + (size_t)(uint32_t)cj * A.ldk);
+                    else
+                        s = att_score<VT, VEC>(q, Kh + (size_t)(uint32_t)cj * A.ldk, A.k);
                     if constexpr (ARGS::EDGE)
                         s = att_bias_score(A.bias, h, s,
                                            att_edge_value(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)(base + jj), h));
@@ -380,6 +414,14 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_edge(const AttEdgeArgs<V
     CSR5_ATTENTION_KERNEL_BODY(true)
 }
 
+// the additive score likewise.  It takes element loads only, so there is one kernel per value type, whatever the launcher's VEC
+template <typename VT>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_gat(const AttGatArgs<VT> A)
+{
+    constexpr bool VEC = false;
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+
 // 16-bit operands, float arithmetic: always the packed, edge-biased call.  7 waves per SIMD are k_attention_edge<float, ..>'s: left to
 // itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 75 registers (6 waves)
 #if defined(__HIP__)
@@ -410,6 +452,11 @@ template <bool VEC, bool MH, typename VT>
 static void attention_enqueue(const AttEdgeArgs<VT> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_edge<VT, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttGatArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_gat<VT>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 template <bool VEC, bool MH, typename ST>
 static void attention_enqueue(const AttLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
@@ -464,7 +511,11 @@ hipError_t attention_launch(const Geometry &g, const DeviceArrays &d, const AttC
     attention_fill<ST>(A, g, d, c);
     if constexpr (ARGS::BIASED)
         att_set_bias(A.bias, d, nullptr, c);
-    const bool vec = attention_vec<ST>(c.heads, c.Q, c.ldq, c.K, c.ldk, c.k);
+    if constexpr (ARGS::GAT)
+        att_set_gat(A.gat, c);
+    bool vec = false; // (the additive score takes element loads: one kernel, whatever the alignment of Q and K)
+    if constexpr (!ARGS::GAT)
+        vec = attention_vec<ST>(c.heads, c.Q, c.ldq, c.K, c.ldk, c.k);
     const unsigned blocks = (unsigned)(((long long)g.m + AT_BLOCK - 1) / AT_BLOCK);
     if (c.heads == 1) {
         const dim3 grid(blocks);

@@ -489,7 +489,7 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
 }
 
 // ---- attention on the pattern (csr5_attention*.hip) ---------------------------------------------------------------------------
-// The ten entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
+// The twelve entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
 // trivial cases, the launch.  The single-head calls are heads = 1.  The forward reads row_ptr, tile_ptr and the tile-ordered
 // column_index of the parent, whatever path spmv() takes (biased: its tile-ordered values too); it allocates nothing and changes
 // nothing: enqueue-only.  lowp: the call names the type its operands are stored in (operand_type, judged here); the others take the handle's.
@@ -499,7 +499,7 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
         return CSR5HIP_INVALID_ARGUMENT;
     if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
         return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
-    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope))
         return CSR5HIP_INVALID_ARGUMENT;
     const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
     if (c.ldq < wk || c.ldk < wk || c.ldv < wd || c.ldo < wd || (c.B && c.ldb < c.heads))
@@ -521,6 +521,8 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
         HIP_TRY(launch_mha(h->g, h->d, h->value_type, c, h->stream));
     else if (variant == ATT_BIASED)
         HIP_TRY(launch_mha_biased(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_GAT)
+        HIP_TRY(launch_gat(h->g, h->d, h->value_type, c, h->stream));
     else
         HIP_TRY(launch_mha_edge(h->g, h->d, h->value_type, c, h->stream));
     return CSR5HIP_SUCCESS;
@@ -537,14 +539,14 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         return CSR5HIP_INVALID_ARGUMENT;
     if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
         return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
-    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale))
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope))
         return CSR5HIP_INVALID_ARGUMENT;
     const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
     if (c.ldq < wk || c.ldk < wk || c.lddq < wk || c.lddk < wk || c.ldv < wd || c.lddo < wd || c.lddv < wd ||
-        (c.B && c.ldb < c.heads) || (c.dS && c.ldds < c.heads))
+        (c.B && c.ldb < c.heads) || (c.dS && c.ldds < c.heads) || (c.dAr && c.lddar < wk))
         return CSR5HIP_INVALID_ARGUMENT;
     const bool column = c.dK || c.dV; // the column side: needs the workspace and the companion
-    const bool any = c.dQ || column || c.dS;
+    const bool any = c.dQ || column || c.dS || c.dAr; // (dAr: gat's second row-side output, null in every other call)
     const int nnz = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5 ? h->g.nnz : 0;
     if (c.heads > 0 && any && nnz > 0 && ((c.k > 0 && (!c.Q || !c.K)) || (c.d > 0 && (!c.V || !c.dO)) || (column && !c.work)))
         return CSR5HIP_INVALID_ARGUMENT;
@@ -560,9 +562,12 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         return CSR5HIP_SUCCESS;
     const size_t vs = lowp ? 2 : h->vsize(); // (lowp: the word 0x0000 is +0 in both 16-bit types)
     // no entries (and then no companion arrays, and no element of dS / dB): the zeros
-    if (nnz == 0 || (column && (!h->comp.at || (variant == ATT_EDGE && !h->comp[A_MAP].ptr)))) {
+    const bool mapped = variant == ATT_EDGE || variant == ATT_GAT; // the column kernel finds B's element through the source map
+    if (nnz == 0 || (column && (!h->comp.at || (mapped && !h->comp[A_MAP].ptr)))) {
         if (c.dQ && c.k > 0 && h->g.m > 0)
             HIP_TRY(hipMemset2DAsync(c.dQ, (size_t)c.lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
+        if (c.dAr && c.k > 0 && h->g.m > 0)
+            HIP_TRY(hipMemset2DAsync(c.dAr, (size_t)c.lddar * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
         if (c.dK && c.k > 0 && h->g.n > 0)
             HIP_TRY(hipMemset2DAsync(c.dK, (size_t)c.lddk * vs, 0, (size_t)wk * vs, (size_t)h->g.n, h->stream));
         if (c.dV && c.d > 0 && h->g.n > 0)
@@ -572,7 +577,7 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
     if (column) {
         c.gt = &h->comp.at->g;
         c.dt = &h->comp.at->d;
-        c.map = variant == ATT_EDGE ? (const uint32_t *)h->comp[A_MAP].ptr : nullptr;
+        c.map = mapped ? (const uint32_t *)h->comp[A_MAP].ptr : nullptr;
     }
     if (lowp)
         HIP_TRY(launch_mha_lowp_bwd(h->g, h->d, operand_type, c, h->stream));
@@ -580,6 +585,8 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         HIP_TRY(launch_mha_bwd(h->g, h->d, h->value_type, c, h->stream));
     else if (variant == ATT_BIASED)
         HIP_TRY(launch_mha_biased_bwd(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_GAT)
+        HIP_TRY(launch_gat_bwd(h->g, h->d, h->value_type, c, h->stream));
     else
         HIP_TRY(launch_mha_edge_bwd(h->g, h->d, h->value_type, c, h->stream));
     return CSR5HIP_SUCCESS;
@@ -687,6 +694,27 @@ int csr5hip_mha_lowp_backward(csr5hip_handle h, int operand_type, int heads, dou
     AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
     c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
     return attention_backward(h, "csr5hip_mha_lowp_backward", ATT_EDGE, true, operand_type, c);
+}
+
+// additive attention (csr5hip_gat.h): the edge call's descriptor with the attention vector and the slope; the kernels read the
+// parent's pattern and nothing of its values
+int csr5hip_gat(csr5hip_handle h, int heads, double negative_slope, const void *d_a, double scale, const void *d_B, int ldb,
+                const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo)
+{
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.a = d_a; c.negative_slope = negative_slope;
+    return attention_forward(h, ATT_GAT, false, 0, c);
+}
+
+int csr5hip_gat_backward(csr5hip_handle h, int heads, double negative_slope, const void *d_a, double scale, const void *d_B, int ldb,
+                         const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO,
+                         int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dB, int lddb,
+                         void *d_dAr, int lddar)
+{
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb; c.a = d_a; c.negative_slope = negative_slope;
+    c.dAr = d_dAr; c.lddar = lddar;
+    return attention_backward(h, "csr5hip_gat_backward", ATT_GAT, false, 0, c);
 }
 
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------

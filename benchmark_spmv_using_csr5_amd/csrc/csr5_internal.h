@@ -265,6 +265,8 @@ struct AttCall {
     const void *slopes; // biased: b = slopes[h] * a_e, a_e the entry's value in d.val; `heads` device values, or null (b = a_e)
     const void *B;      // edge: b = B[e * ldb + h], e the entry's CSR rank; a caller's nnz x heads device values, or null (b = +0)
     int ldb;
+    const void *a;         // gat: the attention vector, heads x k contiguous device values, or null (a = 1)
+    double negative_slope; // gat: the slope of the LeakyReLU for u <= 0, converted once to the value type
 };
 // One call of the backward: the forward's operands, the gradient of O, the wanted outputs (null: not wanted; EVERY row of a wanted
 // one is written in its heads k / heads d columns) and the transposed companion the column kernel walks (gt, dt; edge: and its source
@@ -282,11 +284,13 @@ struct AttBwdCall : AttCall {
     void *work;
     void *dS;
     int ldds;
+    void *dAr;          // gat: the row's share of a's gradient, (m, heads k), written by the row kernel as dQ is; null: not wanted
+    int lddar;
     const Geometry *gt;
     const DeviceArrays *dt;
     const uint32_t *map;
 };
-enum AttVariant { ATT_PLAIN, ATT_BIASED, ATT_EDGE };
+enum AttVariant { ATT_PLAIN, ATT_BIASED, ATT_EDGE, ATT_GAT };
 // the type of the launcher templates' instantiations (attention_launch, attention_bwd_launch), one per unit and operand type
 using AttLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttCall &, hipStream_t);
 using AttBwdLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttBwdCall &, hipStream_t);
@@ -297,6 +301,9 @@ using AttBwdLaunch = hipError_t(const Geometry &, const DeviceArrays &, const At
 hipError_t launch_mha(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
 hipError_t launch_mha_biased(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
 hipError_t launch_mha_edge(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
+// csr5_attention_gat.hip: the edge call with the additive score z = sum_c a_c LeakyReLU(q_c + k_c) in place of the dot product (c.a,
+// c.negative_slope); d.val is NOT read
+hipError_t launch_gat(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
 // csr5_attention_lowp.hip: launch_mha_edge on operands stored in 16 bits (operand_type: CSR5HIP_BF16 or CSR5HIP_F16, checked by the
 // caller; B, Q, K, V, O all of that type, leading dimensions in its elements), float arithmetic, O rounded once.  d.val is NOT read
 hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand_type, const AttCall &c, hipStream_t s);
@@ -307,6 +314,9 @@ hipError_t launch_mha_lowp(const Geometry &g, const DeviceArrays &d, int operand
 hipError_t launch_mha_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_mha_biased_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_mha_edge_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+// csr5_attention_bwd_gat.hip: launch_gat's gradients; the row kernel also writes c.dAr, the column kernel walks the companion with its
+// source map as the edge call's does.  Neither d.val nor c.dt->val is read
+hipError_t launch_gat_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 // csr5_attention_bwd_lowp.hip: launch_mha_edge_bwd on operands stored in 16 bits (operand_type: CSR5HIP_BF16 or CSR5HIP_F16, checked by
 // the caller; B, Q, K, V, dO and dQ, dK, dV, dS all of that type, leading dimensions in its elements), float arithmetic, every output
 // rounded once; c.work is FLOAT, 4 m heads values.  Neither d.val nor c.dt->val is read

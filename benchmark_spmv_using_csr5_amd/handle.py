@@ -646,6 +646,90 @@ class anonymouslibHandle:
                                                    _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work), _ptr(dB),
                                                    int(lddb))
 
+    # -- additive (GAT, GATv2) attention: the non-linearity inside the score (csr5hip_gat.h csr5hip_gat and its backward) -------
+    def _gat_args(self, who: str, Q, a, negative_slope):
+        """the checks of ``negative_slope`` and ``a``, made after those of scale, B and dB and before those of the operands:
+        ValueError unless negative_slope is a finite number and a (or None) is a contiguous (H, k) GPU tensor of the handle's
+        dtype, H and k those Q announces.  Returns the slope as a float."""
+        import math
+        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
+            raise ValueError(f"{who}: negative_slope must be a finite Python number, not {negative_slope!r}")
+        if a is not None:
+            if not hasattr(a, "data_ptr") or not hasattr(a, "is_contiguous"):
+                raise ValueError(f"{who}: a must be a torch tensor or None")
+            if str(a.dtype) != dt:
+                raise ValueError(f"{who}: a has dtype {a.dtype}, the handle holds {dt}")
+            want = (int(Q.shape[1]), int(Q.shape[2])) if hasattr(Q, "dim") and Q.dim() == 3 else None  # (else _mha_args rejects Q)
+            if a.dim() != 2 or (want is not None and tuple(a.shape) != want):
+                raise ValueError(f"{who}: a must have shape (heads, k) = {want}, not {tuple(a.shape)}")
+            if not a.is_contiguous():
+                raise ValueError(f"{who}: a must be contiguous, not stride {a.stride()}")
+            if a.device.type != "cuda":
+                raise ValueError(f"{who}: a must live on the GPU, not {a.device}")
+        return float(negative_slope)
+
+    def gat(self, Q, K, V, O, a=None, negative_slope=0.2, B=None, scale=1.0) -> int:
+        """additive attention in ONE launch: ``mhaEdgeBias`` with the score ``scale * sum_c a[h, c] LeakyReLU(Q[i, h, c] +
+        K[j, h, c]) + B[e, h]`` in the dot product's place.  GAT is k = 1 with ``a=None`` (Q = el, K = er: s = LeakyReLU(el[i] +
+        er[j])); GATv2 is k = the feature width with ``a`` of shape (H, k), contiguous, of the handle's dtype.  Per channel
+        u = q + k, l = u > 0 ? u : negative_slope * u, z = fma(a, l, z) (``a=None``: a = 1), then s = fma(z, scale, B[e, h]), every
+        operation rounded once; everything after the score is ``mha``'s.  Operands, ``B`` and ``scale`` as ``mhaEdgeBias``;
+        ``negative_slope`` is a finite Python number.  Nothing of length nnz is written; THE HANDLE'S VALUES ARE NOT READ and nothing
+        of the handle changes.  Anything else raises ValueError before the library is called."""
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        scale, ldb, _ = self._mha_edge_args("gat", self._mha_heads(Q), scale, B, None, ())
+        ns = self._gat_args("gat", Q, a, negative_slope)
+        heads, k, d = self._mha_args("gat", ins, (("O", O, self._m, "d"),), None)
+        for name, t in (("B", B), ("a", a)):
+            if t is not None and O.numel() and t.numel() and O.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                raise ValueError(f"gat: O shares storage with {name} (aliased)")
+        self._mha_edge_device("gat", Q, (("B", B), ("a", a)))
+        ld = self._mha_ld
+        return self.gat_ptr(heads, ns, a, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+
+    def gat_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int,
+                d: int, O, ldo: int) -> int:
+        """csr5hip_gat on raw device pointers (or tensors); a None for a = 1, B None for no bias"""
+        return self._lib.csr5hip_gat(self._h, int(heads), float(negative_slope), _ptr(a), float(scale), _ptr(B), int(ldb), _ptr(Q),
+                                     int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo))
+
+    def gatBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None, a=None, negative_slope=0.2, B=None, scale=1.0, dB=None,
+                    dAr=None) -> int:
+        """the gradients of ``gat`` in TWO launches: operands, outputs, ``work``, ``B``, ``scale`` and ``dB`` as
+        ``mhaEdgeBiasBackward``, ``a`` and ``negative_slope`` as in the forward.  ``dAr`` (optional): an (m, H, k) tensor, judged as
+        dQ is, that receives THE ROW'S SHARE of the gradient of ``a``: the gradient of ``a`` is ``dAr.sum(0)``.  dK and dV need
+        ``work`` and the transposed companion; dQ, dAr and dB neither.  An output shares storage with no other argument.  The
+        handle's values, the companion's included, are not read.  Anything else raises ValueError before the library is called."""
+        who = "gatBackward"
+        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d"),
+                                 ("dAr", dAr, self._m, "k")) if o[1] is not None)
+        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work), ("a", a))
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others)
+        ns = self._gat_args(who, Q, a, negative_slope)
+        heads, k, d = self._mha_args(who, ins, outs, work)
+        for name, t in (("B", B), ("a", a)):
+            if t is not None:
+                for oname, o, _, _ in outs:
+                    if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                        raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
+        self._mha_edge_device(who, Q, (("B", B), ("dB", dB), ("a", a)))
+        ld = self._mha_ld
+        return self.gat_backward_ptr(heads, ns, a, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
+                                     ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k, dV,
+                                     ld(dV) if dV is not None else heads * d, work, dB, lddb, dAr,
+                                     ld(dAr) if dAr is not None else heads * k)
+
+    def gat_backward_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
+                         ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int, dAr,
+                         lddar: int) -> int:
+        """csr5hip_gat_backward on raw device pointers (or tensors); None for a, for B or for an output that is not wanted"""
+        return self._lib.csr5hip_gat_backward(self._h, int(heads), float(negative_slope), _ptr(a), float(scale), _ptr(B), int(ldb),
+                                              _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO),
+                                              int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
+                                              _ptr(dB), int(lddb), _ptr(dAr), int(lddar))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

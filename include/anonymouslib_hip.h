@@ -252,6 +252,28 @@ public:
                                                    lddk, (void *)dV, lddv, (void *)work, (void *)dB, lddb)
                   : _err;
     }
+    // extension: additive (GAT, GATv2) attention: mhaEdgeBias with the score fma(sum_c a[h k + c] LeakyReLU(Q[i, h, c] + K[j, h, c]),
+    // scale, B[e ldb + h]); a: heads k contiguous device values or null (a = 1); GAT is k = 1 without a (csr5hip_gat)
+    int gat(int heads, double negative_slope, const ANONYMOUSLIB_VT *a, double scale, const ANONYMOUSLIB_VT *B, int ldb,
+            const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,
+            ANONYMOUSLIB_VT *O, int ldo)
+    {
+        return _h ? csr5hip_gat(_h, heads, negative_slope, (const void *)a, scale, (const void *)B, ldb, (const void *)Q, ldq,
+                                (const void *)K, ldk, k, (const void *)V, ldv, d, (void *)O, ldo)
+                  : _err;
+    }
+    // extension: gat's gradients in two launches, operands and dB as mhaEdgeBiasBackward; dAr (or null): m x heads k values, the row's
+    // share of the gradient of a, whose gradient is the sum of dAr over the rows (csr5hip_gat_backward)
+    int gatBackward(int heads, double negative_slope, const ANONYMOUSLIB_VT *a, double scale, const ANONYMOUSLIB_VT *B, int ldb,
+                    const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,
+                    const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk,
+                    ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work, ANONYMOUSLIB_VT *dB, int lddb, ANONYMOUSLIB_VT *dAr, int lddar)
+    {
+        return _h ? csr5hip_gat_backward(_h, heads, negative_slope, (const void *)a, scale, (const void *)B, ldb, (const void *)Q, ldq,
+                                         (const void *)K, ldk, k, (const void *)V, ldv, d, (const void *)dO, lddo, (void *)dQ, lddq,
+                                         (void *)dK, lddk, (void *)dV, lddv, (void *)work, (void *)dB, lddb, (void *)dAr, lddar)
+                  : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

@@ -459,6 +459,10 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads,
 /* Extension (not in the reference): csr5hip_mha_lowp -- csr5hip_mha_edge_bias on operands stored in bf16 or fp16, computed in fp32
  * and rounded once -- is declared, with its contract and its operand-type constants, in csr5hip_lowp.h, which this header includes at
  * its end for the same reason; its declaration and export are compared by tests/test_mha_lowp_host.py. */
+/* Extension (not in the reference): csr5hip_gat and csr5hip_gat_backward -- additive (GAT, GATv2) attention, whose score
+ * fma(sum_c a_c LeakyReLU(q_c + k_c), scale, B) no choice of Q, K and B turns into a dot product -- are declared, with their contracts,
+ * in csr5hip_gat.h, which this header includes at its end for the same reason; their declarations and exports are compared by
+ * tests/test_gat_host.py. */
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -641,6 +645,7 @@ int csr5hip_multi_destroy(csr5hip_multi mh);
 #include "csr5hip_bias.h"
 #include "csr5hip_edge_bias.h"
 #include "csr5hip_lowp.h"
+#include "csr5hip_gat.h"
 
 #ifdef __cplusplus
 }
