@@ -218,8 +218,8 @@ SYMBOLS_LOWP = [
 ]
 
 # its backward, bound by load() like the others: the operand type, then csr5hip_mha_edge_bias_backward's arguments.  A list of its own:
-# tests/test_mha_lowp_host.py pins SYMBOLS_LOWP to its one entry and tests/test_attention_entry_points_host.py the four lists above
-# to nine attention names; tests/test_mha_lowp_backward_host.py compares this one with the export and the header.
+# tests/test_mha_lowp_host.py pins SYMBOLS_LOWP to its one entry; tests/test_mha_lowp_backward_host.py compares this one with the export
+# and the header, and tests/test_attention_entry_points_host.py pins all six lists to the twelve attention names of its table.
 SYMBOLS_LOWP_BACKWARD = [
     ("csr5hip_mha_lowp_backward", C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,

@@ -68,6 +68,12 @@ def _on_current_stream(A, device) -> None:
     _check(A.setStream(torch.cuda.current_stream(device)), "setStream")
 
 
+def _with_transpose(A) -> None:
+    """the transposed companion, built (once per conversion: it allocates and synchronises) unless the handle has it"""
+    if not A.info().transpose_built:
+        _check(A.buildTranspose(), "buildTranspose")
+
+
 def _give_values(A, val, key) -> None:
     """updateValues(val) unless the handle holds exactly these values"""
     if getattr(A, "_autograd_key", None) == key:
@@ -112,8 +118,7 @@ class _Spmm(torch.autograd.Function):
             _check(A.sddmm(dY, X, grad_val), "sddmm")
         if need_X:
             _give_values(A, val, ctx.key)  # (another forward may have given the handle other values: A^T must hold the forward's)
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
+            _with_transpose(A)
             grad_X = torch.zeros((A._n, dY.shape[1]), dtype=dY.dtype, device=dY.device)
             _check(A.spmmT(dY, grad_X), "spmmT")
         return None, grad_val, grad_X
@@ -151,8 +156,7 @@ class _Sddmm(torch.autograd.Function):
             grad_U = torch.zeros((A._m, V.shape[1]), dtype=G.dtype, device=G.device)
             _check(A.spmm(V, grad_U), "spmm")
         if need_V:  # dV[j, :] = sum_i G[i, j] U[i, :]
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
+            _with_transpose(A)
             grad_V = torch.zeros((A._n, U.shape[1]), dtype=G.dtype, device=G.device)
             _check(A.spmmT(U, grad_V), "spmmT")
         return None, grad_U, grad_V
@@ -229,14 +233,7 @@ class _FusedAttention(torch.autograd.Function):
 def _fused_backward(A, saved, need, dO):
     """(dQ, dK, dV), None where not needed, by ONE ``A.attentionBackward`` on the current stream"""
     Q, K, V = saved
-    dO = _rows_unit_stride(dO.detach())
-    _on_current_stream(A, dO.device)
-    outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(saved, need)]
-    work = None
-    if need[1] or need[2]:
-        if not A.info().transpose_built:
-            _check(A.buildTranspose(), "buildTranspose")
-        work = torch.empty(4 * A._m, dtype=dO.dtype, device=dO.device)
+    dO, outs, work = _backward_plumbing(A, saved, need, dO, None, dO.dtype)
     _check(A.attentionBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work), "attentionBackward")
     return tuple(outs)
 
@@ -275,6 +272,33 @@ def _packed(t):
     return t.contiguous()
 
 
+def _backward_plumbing(A, saved, need, dO, heads, work_dtype):
+    """what every backward that is one library call does first, in this order: dO made what the call takes (``heads`` None: the
+    2-D call), the handle put on the current stream, a ``torch.empty`` output for exactly those of ``saved`` (Q, K, V) that
+    ``need`` a gradient, and -- only when K or V needs one -- the transposed companion (``_with_transpose``) and a
+    workspace of 4 m heads values of ``work_dtype``.  Returns (dO, [dQ, dK, dV] with None where not needed, work or None)."""
+    dO = _backward_dO(A, dO, heads)
+    return (dO,) + _backward_buffers(A, saved, need, dO.device, heads, work_dtype)
+
+
+def _backward_dO(A, dO, heads):
+    """the first half of ``_backward_plumbing``: dO as the call takes it, the handle on the current stream"""
+    dO = (_rows_unit_stride if heads is None else _packed)(dO.detach())
+    _on_current_stream(A, dO.device)
+    return dO
+
+
+def _backward_buffers(A, saved, need, device, heads, work_dtype):
+    """the second half: the outputs, the companion and the workspace.  On their own for ``_BiasedMultiheadAttention``, which gives
+    the handle its values between the two: after the stream is set, before anything is allocated"""
+    outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(saved, need)]
+    work = None
+    if need[1] or need[2]:
+        _with_transpose(A)
+        work = torch.empty(4 * A._m * (heads or 1), dtype=work_dtype, device=device)
+    return outs, work
+
+
 class _MultiheadAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, Q, K, V):
@@ -292,14 +316,7 @@ class _MultiheadAttention(torch.autograd.Function):
         if not any(need):
             return None, None, None, None
         A, saved = ctx.A, ctx.saved_tensors
-        dO = _packed(dO.detach())
-        _on_current_stream(A, dO.device)
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(saved, need)]
-        work = None
-        if need[1] or need[2]:
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
-            work = torch.empty(4 * A._m * saved[0].shape[1], dtype=dO.dtype, device=dO.device)
+        dO, outs, work = _backward_plumbing(A, saved, need, dO, saved[0].shape[1], dO.dtype)
         _check(A.mhaBackward(saved[0], saved[1], saved[2], dO, outs[0], outs[1], outs[2], work), "mhaBackward")
         return (None,) + tuple(outs)
 
@@ -334,19 +351,13 @@ class _BiasedMultiheadAttention(torch.autograd.Function):
         if not (any(need) or need_bias or need_slopes):
             return (None,) * 7
         A = ctx.A
-        dO = _packed(dO.detach())
-        _on_current_stream(A, dO.device)
+        dO = _backward_dO(A, dO, Q.shape[1])
         if val is not None:
             _give_values(A, val, ctx.key)  # (another forward may have given the handle other values: both kernels read the forward's)
         elif getattr(A, "_autograd_key", None) != ctx.key:
             raise RuntimeError("multihead_attention: the handle's values were replaced between this forward (bias=None: whatever the "
                                "handle held) and its backward; give the bias as a tensor, which backward hands to the handle again")
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
-        work = None
-        if need[1] or need[2]:
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
-            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        outs, work = _backward_buffers(A, (Q, K, V), need, dO.device, Q.shape[1], dO.dtype)
         dS = torch.empty((A._nnz, Q.shape[1]), dtype=dO.dtype, device=dO.device) if need_bias or need_slopes else None
         _check(A.mhaBiasedBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, scale=ctx.scale, slopes=sl, dS=dS), "mhaBiasedBackward")
         grad_bias = grad_slopes = None
@@ -384,14 +395,7 @@ class _EdgeBiasMultiheadAttention(torch.autograd.Function):
             return (None,) * 6
         A = ctx.A
         Q, K, V, B = ctx.saved_tensors
-        dO = _packed(dO.detach())
-        _on_current_stream(A, dO.device)
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
-        work = None
-        if need[1] or need[2]:
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
-            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], dO.dtype)
         dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
         _check(A.mhaEdgeBiasBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaEdgeBiasBackward")
         return (None,) + tuple(outs) + (None, dB)  # (dB IS the gradient of the bias: no reduction)
@@ -422,33 +426,18 @@ class _LowpMultiheadAttention(torch.autograd.Function):
         if not (any(need) or need_bias):
             return (None,) * 6
         A = ctx.A
-        if A._vt != _capi.F64:
-            Q, K, V = ctx.saved_tensors[:3]
-            B = ctx.saved_tensors[3] if ctx.has_bias else None
-            dO = _packed(dO.detach())
-            _on_current_stream(A, dO.device)
-            outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
-            work = None
-            if need[1] or need[2]:
-                if not A.info().transpose_built:
-                    _check(A.buildTranspose(), "buildTranspose")
-                work = torch.empty(4 * A._m * Q.shape[1], dtype=torch.float32, device=dO.device)
-            dB = torch.empty(tuple(B.shape), dtype=B.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        Q, K, V = ctx.saved_tensors[:3]
+        B = ctx.saved_tensors[3] if ctx.has_bias else None
+        low, stopgap = Q.dtype, A._vt == _capi.F64
+        if stopgap:  # (a widened temporary each: what the fp32 handle's route does not make)
+            Q, K, V = (t.to(torch.float64) for t in (Q, K, V))
+            B = B.to(torch.float64) if B is not None else None
+            dO = _packed(dO.detach()).to(torch.float64)
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], torch.float64 if stopgap else torch.float32)
+        dB = torch.empty(tuple(B.shape), dtype=B.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        if not stopgap:
             _check(A.mhaLowpBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaLowpBackward")
             return (None,) + tuple(outs) + (None, dB)  # (dB IS the gradient of the bias: no reduction, no cast)
-        low = ctx.saved_tensors[0].dtype
-        wide = torch.float64
-        Q, K, V = (t.to(wide) for t in ctx.saved_tensors[:3])  # (a temporary each: what the fp32 handle's route does not make)
-        B = ctx.saved_tensors[3].to(wide) if ctx.has_bias else None
-        dO = _packed(dO.detach()).to(wide)
-        _on_current_stream(A, dO.device)
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
-        work = None
-        if need[1] or need[2]:
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
-            work = torch.empty(4 * A._m * Q.shape[1], dtype=wide, device=dO.device)
-        dB = torch.empty(tuple(B.shape), dtype=wide, device=dO.device) if need_bias else None
         _check(A.mhaEdgeBiasBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, B=B, scale=ctx.scale, dB=dB), "mhaEdgeBiasBackward")
         return (None,) + tuple(o.to(low) if o is not None else None for o in outs) + (None, dB.to(low) if dB is not None else None)
 
@@ -541,14 +530,7 @@ class _GatAttention(torch.autograd.Function):
         if not (any(need) or need_att or need_bias):
             return (None,) * 8
         A = ctx.A
-        dO = _packed(dO.detach())
-        _on_current_stream(A, dO.device)
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip((Q, K, V), need)]
-        work = None
-        if need[1] or need[2]:
-            if not A.info().transpose_built:
-                _check(A.buildTranspose(), "buildTranspose")
-            work = torch.empty(4 * A._m * Q.shape[1], dtype=dO.dtype, device=dO.device)
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], dO.dtype)
         dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
         dAr = torch.empty_like(Q, memory_format=torch.contiguous_format) if need_att else None  # (every row and head is written)
         _check(A.gatBackward(Q, K, V, dO, outs[0], outs[1], outs[2], work, a=a, negative_slope=ctx.ns, B=B, scale=ctx.scale, dB=dB,

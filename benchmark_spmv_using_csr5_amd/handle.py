@@ -9,6 +9,7 @@ permutes the caller's ``col_idx`` / ``val`` tensors in place, exactly as the ref
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -46,6 +47,19 @@ def _value_type(dtype) -> int:
                     "(README.md:71 of the reference)")
 
 
+def _aliased(a, b) -> bool:
+    """whether two tensors are views of one storage (tensors without elements own no memory: their storages all report the same
+    null pointer and alias nothing)"""
+    return bool(a.numel() and b.numel()) and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
+def _finite(who: str, name: str, x) -> float:
+    """``scale`` and ``negative_slope``: ValueError unless x is a finite Python number"""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+        raise ValueError(f"{who}: {name} must be a finite Python number, not {x!r}")
+    return float(x)
+
+
 class anonymouslibHandle:
     """``A = anonymouslibHandle(m, n, dtype)``; then ``inputCSR / setX / setSigma / asCSR5 / spmv /
     destroy`` as in CSR5_cuda/main.cu:59-104."""
@@ -62,6 +76,10 @@ class anonymouslibHandle:
         self._nnz = None  # known after inputCSR
         if stream is not None:
             self.setStream(stream)
+
+    def _dtype_name(self) -> str:
+        """the handle's dtype as ``str(tensor.dtype)`` spells it"""
+        return "torch.float64" if self._vt == _capi.F64 else "torch.float32"
 
     # -- reference API ------------------------------------------------------------------------
     def warmup(self) -> int:
@@ -101,7 +119,7 @@ class anonymouslibHandle:
 
     def _spmm_args(self, who: str, X, x_rows: int, Y, y_rows: int):
         """the checks of spmm / spmmT: (X, ldx, k, Y, ldy) for the C call, or ValueError"""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        dt = self._dtype_name()
         for name, t, rows in (("X", X, x_rows), ("Y", Y, y_rows)):
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"{who}: {name} must be a torch tensor")
@@ -137,7 +155,7 @@ class anonymouslibHandle:
     def spmvT(self, x, y) -> int:
         """y = A^T x: x (m,) and y (n,) contiguous GPU tensors of the handle's dtype; the handle's own x (setX) is not involved.
         Wrong dtype, device, shape or stride raise ValueError before the library is called."""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        dt = self._dtype_name()
         for name, t, rows in (("x", x, self._m), ("y", y, self._n)):
             if not hasattr(t, "data_ptr") or not hasattr(t, "is_contiguous"):
                 raise ValueError(f"spmvT: {name} must be a torch tensor")
@@ -172,7 +190,7 @@ class anonymouslibHandle:
         tensor of nnz values of the handle's dtype that shares storage with neither U nor V.  The matrix values play no part.
         With U = dY and V = X this is the gradient of ``spmm`` with respect to the stored values.  Anything else raises
         ValueError before the library is called."""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        dt = self._dtype_name()
         for name, t, rows in (("U", U, self._m), ("V", V, self._n)):  # (the checks of _spmm_args; the device comes last)
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"sddmm: {name} must be a torch tensor")
@@ -200,7 +218,7 @@ class anonymouslibHandle:
         if not out.is_contiguous():
             raise ValueError(f"sddmm: out must be contiguous, not stride {out.stride()}")
         for name, t in (("U", U), ("V", V)):
-            if out.numel() and t.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+            if _aliased(out, t):
                 raise ValueError(f"sddmm: out shares storage with {name} (aliased)")
         for name, t in (("U", U), ("V", V), ("out", out)):
             if t.device.type != "cuda":
@@ -213,129 +231,57 @@ class anonymouslibHandle:
         """csr5hip_sddmm on raw device pointers (or tensors): U with leading dimension ldu, V with ldv, out nnz values"""
         return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
 
-    # -- attention on the pattern in one pass (csr5hip.h csr5hip_attention) -------------------------
-    def _attention_args(self, who: str, ins, outs, work):
-        """the checks of ``sddmm``'s operands for ``attention``'s 2-D tensors (rows, width), shaped like ``_mha_args``: ValueError,
-        naming the operand, unless each has the handle's dtype, its row count, stride(1) == 1 and rows that do not overlap; the
-        widths agree; ``work`` (wanted with dK or dV) holds 4 m values; no output shares storage with an input, another output
-        or ``work``; all live on one GPU (the device comes last).  Returns (k, d)."""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        for name, t, rows, width in ins + outs:
-            if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
-                raise ValueError(f"{who}: {name} must be a torch tensor")
-            if str(t.dtype) != dt:
-                raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
-            if t.dim() != 2 or t.shape[0] != rows:
-                raise ValueError(f"{who}: {name} must have shape ({rows}, {width}), not {tuple(t.shape)}")
-            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError(f"{who}: {name} must be row-major with stride(1) == 1, not {t.stride()}")
-            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
-                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < {width} = {t.shape[1]})")
-        Q, V = ins[0][1], ins[2][1]
-        k, d = int(Q.shape[1]), int(V.shape[1])
-        for name, t, _, width in ins[1:] + outs:
-            want = k if width == "k" else d
-            if t.shape[1] != want:
-                first = "Q" if width == "k" else "V"
-                raise ValueError(f"{who}: {first} has {want} columns, {name} {t.shape[1]}")
-        if work is not None or any(name in ("dK", "dV") for name, _, _, _ in outs):
-            if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
-                raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
-            if str(work.dtype) != dt:
-                raise ValueError(f"{who}: work has dtype {work.dtype}, the handle holds {dt}")
-            if work.dim() != 1 or work.shape[0] < 4 * self._m:
-                raise ValueError(f"{who}: work must have shape ({4 * self._m},) or longer, not {tuple(work.shape)}")
-            if not work.is_contiguous():
-                raise ValueError(f"{who}: work must be contiguous, not stride {work.stride()}")
-        if self._nnz is None:
-            raise ValueError(f"{who}: call inputCSR first")
-        scratch = (("work", work, 0, ""),) if work is not None else ()
-        for i, (oname, o, _, _) in enumerate(outs):
-            for name, t, _, _ in ins + outs[:i] + scratch:
-                if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                    raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
-        for name, t, _, _ in ins + outs + scratch:
-            if t.device.type != "cuda":
-                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
-        if any(t.device != Q.device for _, t, _, _ in ins + outs + scratch):
-            raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t, _, _ in ins + outs + scratch))
-        return k, d
+    # -- attention on the pattern: what the twelve wrappers below share (DESIGN.md section 28) ------
+    def _forward_operands(self, Q, K, V, O):
+        """(ins, outs) of a forward for ``_operand_args``: (name, tensor, rows, which width) each"""
+        return (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d")), (("O", O, self._m, "d"),)
 
-    @staticmethod
-    def _attention_ld(t) -> int:
-        return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
-
-    def attention(self, Q, K, V, O) -> int:
-        """O = softmax over every row's stored entries of (Q K^T) times V in ONE launch: row i attends to the columns it stores.
-        Q (m, k), K (n, k), V (n, d) and O (m, d) as ``sddmm``'s operands (stride(1) == 1, leading dimension stride(0), so column
-        slices of wider tensors are legal: one call per head needs no copy); O shares storage with none of the inputs, which may
-        share among themselves.  EVERY row of O is written in columns 0 .. d-1 -- rows without entries with +0 -- so O may be
-        ``torch.empty``.  Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything
-        else raises ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
-        k, d = self._attention_args("attention", ins, (("O", O, self._m, "d"),), None)
-        ld = self._attention_ld
-        return self.attention_ptr(Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
-
-    def attention_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
-        """csr5hip_attention on raw device pointers (or tensors): Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
-        return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
-                                           _ptr(O), int(ldo))
-
-    # -- the gradients of attention in two launches (csr5hip.h csr5hip_attention_backward) -----------
-    def attentionBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
-        """The gradients of ``attention``'s O for Q, K and V from the gradient dO (m, d) arriving for O: dQ (m, k), dK (n, k) and
-        dV (n, d), each written in EVERY row (rows and columns of the matrix without entries with +0, so they may be
-        ``torch.empty``) or None when not wanted.  Operands as ``attention``'s (stride(1) == 1, leading dimension stride(0)); an
-        output shares storage with no input, no other output and not with ``work``.  dK and dV need ``work``, a contiguous 1-D
-        tensor of at least 4 m values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
-        Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything else raises ValueError
-        before the library is called."""
+    def _backward_operands(self, Q, K, V, dO, dQ, dK, dV, work, more=()):
+        """(ins, outs, others) of a backward: ``outs`` holds the outputs that are wanted (not None), ``more`` (``gatBackward``:
+        dAr) among them; ``others`` names everything a per-entry output must not share storage with"""
         ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        k, d = self._attention_args("attentionBackward", ins, outs, work)
-        ld = self._attention_ld
-        return self.attention_backward_ptr(Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ, ld(dQ) if dQ is not None else k,
-                                           dK, ld(dK) if dK is not None else k, dV, ld(dV) if dV is not None else d, work)
+        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) + more if o[1] is not None)
+        return ins, outs, tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
 
-    def attention_backward_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int,
-                               dV, lddv: int, work) -> int:
-        """csr5hip_attention_backward on raw device pointers (or tensors); None for an output that is not wanted"""
-        return self._lib.csr5hip_attention_backward(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
-                                                    _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv),
-                                                    _ptr(work))
-
-    # -- attention for all heads in one launch (csr5hip.h csr5hip_mha / csr5hip_mha_backward) -------
-    def _mha_args(self, who: str, ins, outs, work, dt=None, work_dt=None):
-        """the checks of ``attention``'s operands for packed 3-D tensors (rows, heads, width): ValueError, naming the operand,
-        unless each has the handle's dtype, its row count, stride(2) == 1, stride(1) == width and rows that do not overlap; the
-        head counts and widths agree; no output shares storage with an input, another output or ``work``; all live on one GPU.
-        ``dt``: the dtype the operands must have instead of the handle's (``mhaLowp``: Q's); ``work_dt``: the dtype ``work`` must
-        have instead of the operands' (``mhaLowpBackward``: float32).  Returns (heads, k, d)."""
+    def _operand_args(self, who: str, rank: int, ins, outs, work, dt=None, work_dt=None):
+        """the checks of the operands, 2-D (rows, width) for ``attention`` or packed 3-D (rows, heads, width) for the others
+        (``rank``): ValueError, naming the operand, unless each input and output has the handle's dtype, its row count, a unit
+        inner stride, stride(1) == width (3-D) and rows that do not overlap; the head counts and widths agree; ``work`` (wanted
+        with dK or dV) holds 4 m heads values; ``inputCSR`` was called; no output shares storage with an input, an earlier output
+        or ``work``; all live on one GPU (the device comes last).  ``dt``: the dtype the operands must have instead of the
+        handle's (``mhaLowp``: Q's); ``work_dt``: the dtype ``work`` must have instead of the operands' (``mhaLowpBackward``:
+        float32).  Returns (heads, k, d, ld): heads is 1 for 2-D operands, ld the leading dimension by name, heads * width for a
+        backward's output that is not among ``outs``."""
         holds = "the handle holds" if dt is None else "Q has"
-        dt = dt or ("torch.float64" if self._vt == _capi.F64 else "torch.float32")
+        dt = dt or self._dtype_name()
+        packed = rank == 3
+        per_head, unit = ("heads, ", "have stride(2) == 1") if packed else ("", "be row-major with stride(1) == 1")
         for name, t, rows, width in ins + outs:
             if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
                 raise ValueError(f"{who}: {name} must be a torch tensor")
             if str(t.dtype) != dt:
                 raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
-            if t.dim() != 3 or t.shape[0] != rows:
-                raise ValueError(f"{who}: {name} must have shape ({rows}, heads, {width}), not {tuple(t.shape)}")
-            if t.numel() and t.shape[2] > 1 and t.stride(2) != 1:
-                raise ValueError(f"{who}: {name} must have stride(2) == 1, not {t.stride()}")
-            if t.numel() and t.shape[1] > 1 and t.stride(1) != t.shape[2]:
-                raise ValueError(f"{who}: {name} must be packed with stride(1) == {width} = {t.shape[2]}, not {t.stride()}")
-            if t.numel() and t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2]:
-                raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads * {width} = {t.shape[1] * t.shape[2]})")
+            shape, stride = t.shape, t.stride()
+            if len(shape) != rank or shape[0] != rows:
+                raise ValueError(f"{who}: {name} must have shape ({rows}, {per_head}{width}), not {tuple(shape)}")
+            if not t.numel():
+                continue  # (a tensor without elements has no strides to judge)
+            if shape[-1] > 1 and stride[-1] != 1:
+                raise ValueError(f"{who}: {name} must {unit}, not {stride}")
+            if packed and shape[1] > 1 and stride[1] != shape[2]:
+                raise ValueError(f"{who}: {name} must be packed with stride(1) == {width} = {shape[2]}, not {stride}")
+            row = shape[1] * shape[2] if packed else shape[1]
+            if shape[0] > 1 and stride[0] < row:
+                raise ValueError(f"{who}: {name} rows overlap (stride(0) {stride[0]} < {'heads * ' if packed else ''}{width} = {row})")
         Q, V = ins[0][1], ins[2][1]
-        heads, k, d = int(Q.shape[1]), int(Q.shape[2]), int(V.shape[2])
+        heads, k, d = int(Q.shape[1]) if packed else 1, int(Q.shape[-1]), int(V.shape[-1])
         for name, t, _, width in ins[1:] + outs:
-            if t.shape[1] != heads:
+            if packed and t.shape[1] != heads:
                 raise ValueError(f"{who}: Q has {heads} heads, {name} {t.shape[1]}")
-            want = k if width == "k" else d
-            if t.shape[2] != want:
-                first = "Q" if width == "k" else "V"
-                raise ValueError(f"{who}: {first} has width {want}, {name} {t.shape[2]}")
+            first, want = ("Q", k) if width == "k" else ("V", d)
+            if t.shape[-1] != want:
+                raise ValueError(f"{who}: {first} has width {want}, {name} {t.shape[2]}" if packed else
+                                 f"{who}: {first} has {want} columns, {name} {t.shape[1]}")
         if work is not None or any(name in ("dK", "dV") for name, _, _, _ in outs):
             if not hasattr(work, "data_ptr") or not hasattr(work, "is_contiguous"):
                 raise ValueError(f"{who}: work must be a torch tensor when dK or dV is wanted")
@@ -352,30 +298,172 @@ class anonymouslibHandle:
         scratch = (("work", work, 0, ""),) if work is not None else ()
         for i, (oname, o, _, _) in enumerate(outs):
             for name, t, _, _ in ins + outs[:i] + scratch:
-                if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                if _aliased(o, t):
                     raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
         for name, t, _, _ in ins + outs + scratch:
             if t.device.type != "cuda":
                 raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
         if any(t.device != Q.device for _, t, _, _ in ins + outs + scratch):
             raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t, _, _ in ins + outs + scratch))
-        return heads, k, d
+        ld = dict(dQ=heads * k, dK=heads * k, dV=heads * d, dAr=heads * k)  # (an output that is not wanted)
+        for name, t, _, width in ins + outs:
+            w = heads * (k if width == "k" else d)
+            # (a 2-D operand without columns reports its stride, as it always has; a packed one reports 0)
+            ld[name] = max(int(t.stride(0)), w) if t.shape[0] > 1 and (w or not packed) else w
+        return heads, k, d, ld
 
     @staticmethod
-    def _mha_ld(t) -> int:
-        w = int(t.shape[1]) * int(t.shape[2])
-        return max(int(t.stride(0)), w) if t.shape[0] > 1 and w else w
+    def _mha_heads(Q) -> int:
+        """the head count Q announces (judged by ``_operand_args`` afterwards); 0 when Q is no 3-D tensor, which that check rejects"""
+        return int(Q.shape[1]) if hasattr(Q, "dim") and hasattr(Q, "shape") and Q.dim() == 3 else 0
 
+    def _mha_entry_tensor(self, who: str, name: str, t, heads: int, dt: str, holds: str, others=()) -> int:
+        """the checks of one per-entry tensor (``dS``, ``B``, ``dB``): ValueError unless it is a 2-D tensor of shape (nnz, heads)
+        and dtype ``dt`` with stride(1) == 1 and non-overlapping rows that shares storage with none of the tensors among
+        ``others`` (its device is the caller's to judge).  Returns its row stride; ``heads`` for None."""
+        if t is None:
+            return heads
+        if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+            raise ValueError(f"{who}: {name} must be a torch tensor or None")
+        if str(t.dtype) != dt:
+            raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
+        if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
+            raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
+        if t.numel() and heads > 1 and t.stride(1) != 1:
+            raise ValueError(f"{who}: {name} must have stride(1) == 1, not {t.stride()}")
+        if t.numel() and t.shape[0] > 1 and t.stride(0) < heads:
+            raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads = {heads})")
+        for oname, o in others:  # (judged before the operands: an entry may be None or no tensor at all)
+            if hasattr(o, "data_ptr") and _aliased(t, o):
+                raise ValueError(f"{who}: {name} shares a storage with {oname} (views of one storage are rejected, disjoint or not)")
+        return max(int(t.stride(0)), heads) if t.shape[0] > 1 and heads else heads
+
+    def _small_tensor(self, who: str, name: str, t, rank: int, want, text: str) -> None:
+        """the checks of ``slopes`` and ``a``: ValueError unless t is None or a contiguous GPU tensor of the handle's dtype, of
+        ``rank`` dimensions and, where ``want`` is known, of that shape (``text`` describes it)"""
+        if t is None:
+            return
+        dt = self._dtype_name()
+        if not hasattr(t, "data_ptr") or not hasattr(t, "is_contiguous"):
+            raise ValueError(f"{who}: {name} must be a torch tensor or None")
+        if str(t.dtype) != dt:
+            raise ValueError(f"{who}: {name} has dtype {t.dtype}, the handle holds {dt}")
+        if t.dim() != rank or (want is not None and tuple(t.shape) != want):
+            raise ValueError(f"{who}: {name} must have shape {text}, not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous, not stride {t.stride()}")
+        if t.device.type != "cuda":
+            raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+
+    def _mha_bias_args(self, who: str, heads: int, scale, slopes, dS, others):
+        """the checks of ``scale``, ``slopes`` and ``dS``, made before those of the operands: ValueError unless scale is a finite
+        number, slopes (or None) a contiguous 1-D GPU tensor of ``heads`` values of the handle's dtype, dS (or None) an
+        (nnz, heads) GPU tensor of that dtype with stride(1) == 1 and non-overlapping rows that shares storage with none of
+        ``others``.  Returns (scale, ldds)."""
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        scale = _finite(who, "scale", scale)
+        self._small_tensor(who, "slopes", slopes, 1, (heads,), f"({heads},)")
+        ldds = self._mha_entry_tensor(who, "dS", dS, heads, self._dtype_name(), "the handle holds", others)
+        if dS is not None and dS.device.type != "cuda":
+            raise ValueError(f"{who}: dS must live on the GPU, not {dS.device}")
+        return scale, ldds
+
+    def _mha_edge_args(self, who: str, heads: int, scale, B, dB, others, dt=None):
+        """the checks of ``scale``, ``B`` and ``dB``, made before those of the operands: ValueError unless scale is a finite
+        number and B and dB (or None) are 2-D GPU tensors of shape (nnz, heads) and of the handle's dtype with stride(1) == 1 and
+        non-overlapping rows; dB shares storage with none of ``others`` nor with B.  ``dt``: the dtype B and dB must have instead
+        of the handle's (``mhaLowp``: Q's).  Returns (scale, ldb, lddb): the row strides."""
+        holds = "the handle holds" if dt is None else "Q has"
+        dt = dt or self._dtype_name()
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        scale = _finite(who, "scale", scale)
+        ldb = self._mha_entry_tensor(who, "B", B, heads, dt, holds)
+        lddb = self._mha_entry_tensor(who, "dB", dB, heads, dt, holds, others + (("B", B),))
+        for name, t in (("B", B), ("dB", dB)):
+            if t is not None and t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        return scale, ldb, lddb
+
+    def _gat_args(self, who: str, Q, a, negative_slope):
+        """the checks of ``negative_slope`` and ``a``, made after those of scale, B and dB and before those of the operands:
+        ValueError unless negative_slope is a finite number and a (or None) is a contiguous (H, k) GPU tensor of the handle's
+        dtype, H and k those Q announces.  Returns the slope as a float."""
+        ns = _finite(who, "negative_slope", negative_slope)
+        want = (int(Q.shape[1]), int(Q.shape[2])) if hasattr(Q, "dim") and Q.dim() == 3 else None  # (else _operand_args rejects Q)
+        self._small_tensor(who, "a", a, 2, want, f"(heads, k) = {want}")
+        return ns
+
+    def _after_operands(self, who: str, Q, outs, read, named) -> None:
+        """what is left to judge of the tensors beside the operands once ``_operand_args`` has passed: ValueError if an output
+        of ``outs`` shares storage with an input of ``read`` (B, a), or a tensor of ``named`` is not on Q's device"""
+        for name, t in read:
+            if t is not None:
+                for oname, o, _, _ in outs:
+                    if _aliased(o, t):
+                        raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
+        for name, t in named:
+            if t is not None and t.device != Q.device:
+                raise ValueError(f"{who}: {name} on {t.device}, Q on {Q.device}")
+
+    _LOWP = {"torch.bfloat16": _capi.BF16, "torch.float16": _capi.F16}
+
+    def _lowp_type(self, who: str, Q):
+        """(the operand type of csr5hip_lowp.h, the dtype's name) of a 16-bit Q, or ValueError"""
+        ot = self._LOWP.get(str(getattr(Q, "dtype", None)))
+        if ot is None:
+            raise ValueError(f"{who}: Q must be a torch.bfloat16 or torch.float16 tensor, not {getattr(Q, 'dtype', type(Q).__name__)}")
+        return ot, str(Q.dtype)
+
+    # -- attention on the pattern in one pass (csr5hip.h csr5hip_attention) -------------------------
+    def attention(self, Q, K, V, O) -> int:
+        """O = softmax over every row's stored entries of (Q K^T) times V in ONE launch: row i attends to the columns it stores.
+        Q (m, k), K (n, k), V (n, d) and O (m, d) as ``sddmm``'s operands (stride(1) == 1, leading dimension stride(0), so column
+        slices of wider tensors are legal: one call per head needs no copy); O shares storage with none of the inputs, which may
+        share among themselves.  EVERY row of O is written in columns 0 .. d-1 -- rows without entries with +0 -- so O may be
+        ``torch.empty``.  Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything
+        else raises ValueError before the library is called."""
+        ins, outs = self._forward_operands(Q, K, V, O)
+        _, k, d, ld = self._operand_args("attention", 2, ins, outs, None)
+        return self.attention_ptr(Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
+
+    def attention_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
+        """csr5hip_attention on raw device pointers (or tensors): Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
+        return self._lib.csr5hip_attention(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                           _ptr(O), int(ldo))
+
+    # -- the gradients of attention in two launches (csr5hip.h csr5hip_attention_backward) -----------
+    def attentionBackward(self, Q, K, V, dO, dQ=None, dK=None, dV=None, work=None) -> int:
+        """The gradients of ``attention``'s O for Q, K and V from the gradient dO (m, d) arriving for O: dQ (m, k), dK (n, k) and
+        dV (n, d), each written in EVERY row (rows and columns of the matrix without entries with +0, so they may be
+        ``torch.empty``) or None when not wanted.  Operands as ``attention``'s (stride(1) == 1, leading dimension stride(0)); an
+        output shares storage with no input, no other output and not with ``work``.  dK and dV need ``work``, a contiguous 1-D
+        tensor of at least 4 m values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
+        Nothing of length nnz is written and the handle (its values included) is left untouched.  Anything else raises ValueError
+        before the library is called."""
+        ins, outs, _ = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
+        _, k, d, ld = self._operand_args("attentionBackward", 2, ins, outs, work)
+        return self.attention_backward_ptr(Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"], dK, ld["dK"],
+                                           dV, ld["dV"], work)
+
+    def attention_backward_ptr(self, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int,
+                               dV, lddv: int, work) -> int:
+        """csr5hip_attention_backward on raw device pointers (or tensors); None for an output that is not wanted"""
+        return self._lib.csr5hip_attention_backward(self._h, _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                                    _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv),
+                                                    _ptr(work))
+
+    # -- attention for all heads in one launch (csr5hip.h csr5hip_mha / csr5hip_mha_backward) -------
     def mha(self, Q, K, V, O) -> int:
         """``attention`` for all heads in ONE launch: Q (m, H, k), K (n, H, k), V (n, H, d) and O (m, H, d), packed (stride(2) == 1,
         stride(1) == width; stride(0) >= H * width, so a slice of a wider tensor is legal).  Head h of O has, bit for bit, what
         ``attention(Q[:, h], K[:, h], V[:, h], O[:, h])`` writes; EVERY row of O is written in all H * d columns, so O may be
         ``torch.empty``; O shares storage with none of the inputs.  The handle is left untouched.  Anything else raises
         ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
-        heads, k, d = self._mha_args("mha", ins, (("O", O, self._m, "d"),), None)
-        ld = self._mha_ld
-        return self.mha_ptr(heads, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+        ins, outs = self._forward_operands(Q, K, V, O)
+        heads, k, d, ld = self._operand_args("mha", 3, ins, outs, None)
+        return self.mha_ptr(heads, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
 
     def mha_ptr(self, heads: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
         """csr5hip_mha on raw device pointers (or tensors): packed Q, K, V, O with leading dimensions ldq, ldk, ldv, ldo"""
@@ -389,12 +477,10 @@ class anonymouslibHandle:
         tensor of at least 4 m H values of scratch, and the transposed companion (``buildTranspose``; it is never built here).
         An output shares storage with no input, no other output and not with ``work``.  Anything else raises ValueError before
         the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        heads, k, d = self._mha_args("mhaBackward", ins, outs, work)
-        ld = self._mha_ld
-        return self.mha_backward_ptr(heads, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ, ld(dQ) if dQ is not None else heads * k,
-                                     dK, ld(dK) if dK is not None else heads * k, dV, ld(dV) if dV is not None else heads * d, work)
+        ins, outs, _ = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
+        heads, k, d, ld = self._operand_args("mhaBackward", 3, ins, outs, work)
+        return self.mha_backward_ptr(heads, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"], dK, ld["dK"],
+                                     dV, ld["dV"], work)
 
     def mha_backward_ptr(self, heads: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK,
                          lddk: int, dV, lddv: int, work) -> int:
@@ -404,59 +490,6 @@ class anonymouslibHandle:
                                               int(lddv), _ptr(work))
 
     # -- the same with a softmax scale and a score bias from the stored values (csr5hip.h csr5hip_mha_biased) -------
-    @staticmethod
-    def _mha_heads(Q) -> int:
-        """the head count Q announces (judged by ``_mha_args`` afterwards); 0 when Q is no 3-D tensor, which that check rejects"""
-        return int(Q.shape[1]) if hasattr(Q, "dim") and hasattr(Q, "shape") and Q.dim() == 3 else 0
-
-    def _mha_entry_tensor(self, who: str, name: str, t, heads: int, dt: str, holds: str, others=()) -> int:
-        """the checks of one per-entry tensor (``dS``, ``B``, ``dB``): ValueError unless it is a 2-D tensor of shape (nnz, heads)
-        and dtype ``dt`` with stride(1) == 1 and non-overlapping rows that shares storage with none of ``others`` (its device
-        is the caller's to judge).  Returns its row stride; ``heads`` for None."""
-        if t is None:
-            return heads
-        if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
-            raise ValueError(f"{who}: {name} must be a torch tensor or None")
-        if str(t.dtype) != dt:
-            raise ValueError(f"{who}: {name} has dtype {t.dtype}, {holds} {dt}")
-        if t.dim() != 2 or tuple(t.shape) != (self._nnz, heads):
-            raise ValueError(f"{who}: {name} must have shape ({self._nnz}, {heads}), not {tuple(t.shape)}")
-        if t.numel() and heads > 1 and t.stride(1) != 1:
-            raise ValueError(f"{who}: {name} must have stride(1) == 1, not {t.stride()}")
-        if t.numel() and t.shape[0] > 1 and t.stride(0) < heads:
-            raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < heads = {heads})")
-        for oname, o in others:
-            if hasattr(o, "untyped_storage") and t.numel() and o.numel() and t.untyped_storage().data_ptr() == o.untyped_storage().data_ptr():
-                raise ValueError(f"{who}: {name} shares a storage with {oname} (views of one storage are rejected, disjoint or not)")
-        return max(int(t.stride(0)), heads) if t.shape[0] > 1 and heads else heads
-
-    def _mha_bias_args(self, who: str, heads: int, scale, slopes, dS, others):
-        """the checks of ``scale``, ``slopes`` and ``dS``, made before those of the operands: ValueError unless scale is a finite
-        number, slopes (or None) a contiguous 1-D GPU tensor of ``heads`` values of the handle's dtype, dS (or None) an
-        (nnz, heads) GPU tensor of that dtype with stride(1) == 1 and non-overlapping rows that shares storage with none of
-        ``others``.  Returns (scale, ldds)."""
-        import math
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        if self._nnz is None:
-            raise ValueError(f"{who}: call inputCSR first")
-        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
-            raise ValueError(f"{who}: scale must be a finite Python number, not {scale!r}")
-        if slopes is not None:
-            if not hasattr(slopes, "data_ptr") or not hasattr(slopes, "is_contiguous"):
-                raise ValueError(f"{who}: slopes must be a torch tensor or None")
-            if str(slopes.dtype) != dt:
-                raise ValueError(f"{who}: slopes has dtype {slopes.dtype}, the handle holds {dt}")
-            if slopes.dim() != 1 or slopes.shape[0] != heads:
-                raise ValueError(f"{who}: slopes must have shape ({heads},), not {tuple(slopes.shape)}")
-            if not slopes.is_contiguous():
-                raise ValueError(f"{who}: slopes must be contiguous, not stride {slopes.stride()}")
-            if slopes.device.type != "cuda":
-                raise ValueError(f"{who}: slopes must live on the GPU, not {slopes.device}")
-        ldds = self._mha_entry_tensor(who, "dS", dS, heads, dt, "the handle holds", others)
-        if dS is not None and dS.device.type != "cuda":
-            raise ValueError(f"{who}: dS must live on the GPU, not {dS.device}")
-        return float(scale), ldds
-
     def mhaBiased(self, Q, K, V, O, scale=1.0, slopes=None) -> int:
         """``mha`` on the scores ``scale * Q K^T + slopes[h] * A``: softmax scale and an additive bias from the handle's STORED
         VALUES (what ``inputCSR`` gave or the last ``updateValues``), one value per stored entry, times a slope per head, in ONE
@@ -464,11 +497,10 @@ class anonymouslibHandle:
         value as it is.  A value of -Inf masks its entry.  Operands as ``mha``; ``scale`` is a finite Python number, ``slopes`` a
         contiguous 1-D tensor of H values of the handle's dtype.  The handle's values are read, never written.  Anything else
         raises ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        ins, outs = self._forward_operands(Q, K, V, O)
         scale, _ = self._mha_bias_args("mhaBiased", self._mha_heads(Q), scale, slopes, None, ())
-        heads, k, d = self._mha_args("mhaBiased", ins, (("O", O, self._m, "d"),), None)
-        ld = self._mha_ld
-        return self.mha_biased_ptr(heads, scale, slopes, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+        heads, k, d, ld = self._operand_args("mhaBiased", 3, ins, outs, None)
+        return self.mha_biased_ptr(heads, scale, slopes, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
 
     def mha_biased_ptr(self, heads: int, scale: float, slopes, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O, ldo: int) -> int:
         """csr5hip_mha_biased on raw device pointers (or tensors); slopes None for no slopes"""
@@ -482,15 +514,11 @@ class anonymouslibHandle:
         ``(dS * slopes).sum(1)`` and that of the slopes ``(dS * val[:, None]).sum(0)``.  dK and dV need ``work`` and the
         transposed companion, dS and dQ neither.  The handle's values are read, never written.  Anything else raises ValueError
         before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
         scale, ldds = self._mha_bias_args("mhaBiasedBackward", self._mha_heads(Q), scale, slopes, dS, others)
-        heads, k, d = self._mha_args("mhaBiasedBackward", ins, outs, work)
-        ld = self._mha_ld
-        return self.mha_biased_backward_ptr(heads, scale, slopes, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
-                                            ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k, dV,
-                                            ld(dV) if dV is not None else heads * d, work, dS, ldds)
+        heads, k, d, ld = self._operand_args("mhaBiasedBackward", 3, ins, outs, work)
+        return self.mha_biased_backward_ptr(heads, scale, slopes, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"],
+                                            dK, ld["dK"], dV, ld["dV"], work, dS, ldds)
 
     def mha_biased_backward_ptr(self, heads: int, scale: float, slopes, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, dO,
                                 lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dS, ldds: int) -> int:
@@ -501,30 +529,6 @@ class anonymouslibHandle:
                                                      int(ldds))
 
     # -- the same with a per-head bias from a caller-owned (nnz, H) tensor (csr5hip_edge_bias.h csr5hip_mha_edge_bias) -------
-    def _mha_edge_args(self, who: str, heads: int, scale, B, dB, others, dt=None):
-        """the checks of ``scale``, ``B`` and ``dB``, made before those of the operands: ValueError unless scale is a finite
-        number and B and dB (or None) are 2-D GPU tensors of shape (nnz, heads) and of the handle's dtype with stride(1) == 1 and
-        non-overlapping rows; dB shares storage with none of ``others`` nor with B.  ``dt``: the dtype B and dB must have instead
-        of the handle's (``mhaLowp``: Q's).  Returns (scale, ldb, lddb): the row strides."""
-        import math
-        holds = "the handle holds" if dt is None else "Q has"
-        dt = dt or ("torch.float64" if self._vt == _capi.F64 else "torch.float32")
-        if self._nnz is None:
-            raise ValueError(f"{who}: call inputCSR first")
-        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
-            raise ValueError(f"{who}: scale must be a finite Python number, not {scale!r}")
-        ldb = self._mha_entry_tensor(who, "B", B, heads, dt, holds)
-        lddb = self._mha_entry_tensor(who, "dB", dB, heads, dt, holds, others + (("B", B),))
-        for name, t in (("B", B), ("dB", dB)):
-            if t is not None and t.device.type != "cuda":
-                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
-        return float(scale), ldb, lddb
-
-    def _mha_edge_device(self, who: str, Q, named) -> None:
-        for name, t in named:
-            if t is not None and t.device != Q.device:
-                raise ValueError(f"{who}: {name} on {t.device}, Q on {Q.device}")
-
     def mhaEdgeBias(self, Q, K, V, O, B=None, scale=1.0) -> int:
         """``mha`` on the scores ``scale * Q K^T + B``: softmax scale and an additive bias that differs per stored entry AND per
         head, from the caller's tensor ``B`` of shape (nnz, H) in CSR order (the order ``sddmm`` writes and ``updateValues``
@@ -532,14 +536,11 @@ class anonymouslibHandle:
         stride(1) == 1; its row stride is free (a slice of a wider tensor is legal: the columns beyond H are never read).
         ``B=None`` is no bias.  A bias of -Inf masks its entry in that head.  Operands as ``mha``.  THE HANDLE'S VALUES ARE NOT
         READ and nothing of the handle changes.  Anything else raises ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        ins, outs = self._forward_operands(Q, K, V, O)
         scale, ldb, _ = self._mha_edge_args("mhaEdgeBias", self._mha_heads(Q), scale, B, None, ())
-        heads, k, d = self._mha_args("mhaEdgeBias", ins, (("O", O, self._m, "d"),), None)
-        if B is not None and O.numel() and B.numel() and O.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
-            raise ValueError("mhaEdgeBias: O shares storage with B (aliased)")
-        self._mha_edge_device("mhaEdgeBias", Q, (("B", B),))
-        ld = self._mha_ld
-        return self.mha_edge_bias_ptr(heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+        heads, k, d, ld = self._operand_args("mhaEdgeBias", 3, ins, outs, None)
+        self._after_operands("mhaEdgeBias", Q, outs, (("B", B),), (("B", B),))
+        return self.mha_edge_bias_ptr(heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
 
     def mha_edge_bias_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O,
                           ldo: int) -> int:
@@ -553,20 +554,13 @@ class anonymouslibHandle:
         entry and head by head; no reduction is needed, and columns beyond H of a wider tensor it is a slice of stay untouched.
         dK and dV need ``work`` and the transposed companion, dB and dQ neither.  The handle's values, the companion's included,
         are not read.  Anything else raises ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
-        scale, ldb, lddb = self._mha_edge_args("mhaEdgeBiasBackward", self._mha_heads(Q), scale, B, dB, others)
-        heads, k, d = self._mha_args("mhaEdgeBiasBackward", ins, outs, work)
-        if B is not None:
-            for oname, o, _, _ in outs:
-                if o.numel() and B.numel() and o.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
-                    raise ValueError(f"mhaEdgeBiasBackward: {oname} shares storage with B (aliased)")
-        self._mha_edge_device("mhaEdgeBiasBackward", Q, (("B", B), ("dB", dB)))
-        ld = self._mha_ld
-        return self.mha_edge_bias_backward_ptr(heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
-                                               ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k,
-                                               dV, ld(dV) if dV is not None else heads * d, work, dB, lddb)
+        who = "mhaEdgeBiasBackward"
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work)
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B), ("dB", dB)))
+        return self.mha_edge_bias_backward_ptr(heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"],
+                                               dK, ld["dK"], dV, ld["dV"], work, dB, lddb)
 
     def mha_edge_bias_backward_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int,
                                    dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int) -> int:
@@ -577,8 +571,6 @@ class anonymouslibHandle:
                                                         _ptr(dB), int(lddb))
 
     # -- the same with operands stored in bf16 / fp16, computed in fp32 (csr5hip_lowp.h csr5hip_mha_lowp and its backward) -------
-    _LOWP = {"torch.bfloat16": _capi.BF16, "torch.float16": _capi.F16}
-
     def mhaLowp(self, Q, K, V, O, B=None, scale=1.0) -> int:
         """``mhaEdgeBias`` on operands STORED IN 16 BITS: Q, K, V, O and B (when given) are all ``torch.bfloat16`` or all
         ``torch.float16``, WHATEVER THE HANDLE'S DTYPE -- only its pattern is used, and an fp32 and an fp64 handle give the same
@@ -587,18 +579,12 @@ class anonymouslibHandle:
         operand type.  Layouts, strides, devices and aliasing as ``mhaEdgeBias``; ``B=None`` is no bias, a bias of -Inf masks its
         entry in that head; an fp16 O is +-Inf where the fp32 result exceeds 65 504.  ONE launch; the handle is left untouched.
         Anything else raises ValueError before the library is called."""
-        ot = self._LOWP.get(str(getattr(Q, "dtype", None)))
-        if ot is None:
-            raise ValueError(f"mhaLowp: Q must be a torch.bfloat16 or torch.float16 tensor, not {getattr(Q, 'dtype', type(Q).__name__)}")
-        dt = str(Q.dtype)
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        ot, dt = self._lowp_type("mhaLowp", Q)
+        ins, outs = self._forward_operands(Q, K, V, O)
         scale, ldb, _ = self._mha_edge_args("mhaLowp", self._mha_heads(Q), scale, B, None, (), dt)
-        heads, k, d = self._mha_args("mhaLowp", ins, (("O", O, self._m, "d"),), None, dt)
-        if B is not None and O.numel() and B.numel() and O.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
-            raise ValueError("mhaLowp: O shares storage with B (aliased)")
-        self._mha_edge_device("mhaLowp", Q, (("B", B),))
-        ld = self._mha_ld
-        return self.mha_lowp_ptr(ot, heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+        heads, k, d, ld = self._operand_args("mhaLowp", 3, ins, outs, None, dt)
+        self._after_operands("mhaLowp", Q, outs, (("B", B),), (("B", B),))
+        return self.mha_lowp_ptr(ot, heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
 
     def mha_lowp_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int,
                      d: int, O, ldo: int) -> int:
@@ -618,24 +604,13 @@ class anonymouslibHandle:
         devices and aliasing as ``mhaEdgeBiasBackward``.  The handle's values are not read.  Anything else raises ValueError
         before the library is called."""
         who = "mhaLowpBackward"
-        ot = self._LOWP.get(str(getattr(Q, "dtype", None)))
-        if ot is None:
-            raise ValueError(f"{who}: Q must be a torch.bfloat16 or torch.float16 tensor, not {getattr(Q, 'dtype', type(Q).__name__)}")
-        dt = str(Q.dtype)
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d")) if o[1] is not None)
-        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work),)
+        ot, dt = self._lowp_type(who, Q)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
         scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others, dt)
-        heads, k, d = self._mha_args(who, ins, outs, work, dt, "torch.float32")
-        if B is not None:
-            for oname, o, _, _ in outs:
-                if o.numel() and B.numel() and o.untyped_storage().data_ptr() == B.untyped_storage().data_ptr():
-                    raise ValueError(f"{who}: {oname} shares storage with B (aliased)")
-        self._mha_edge_device(who, Q, (("B", B), ("dB", dB)))
-        ld = self._mha_ld
-        return self.mha_lowp_backward_ptr(ot, heads, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
-                                          ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k,
-                                          dV, ld(dV) if dV is not None else heads * d, work, dB, lddb)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work, dt, "torch.float32")
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B), ("dB", dB)))
+        return self.mha_lowp_backward_ptr(ot, heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"],
+                                          dK, ld["dK"], dV, ld["dV"], work, dB, lddb)
 
     def mha_lowp_backward_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
                               ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int) -> int:
@@ -647,28 +622,6 @@ class anonymouslibHandle:
                                                    int(lddb))
 
     # -- additive (GAT, GATv2) attention: the non-linearity inside the score (csr5hip_gat.h csr5hip_gat and its backward) -------
-    def _gat_args(self, who: str, Q, a, negative_slope):
-        """the checks of ``negative_slope`` and ``a``, made after those of scale, B and dB and before those of the operands:
-        ValueError unless negative_slope is a finite number and a (or None) is a contiguous (H, k) GPU tensor of the handle's
-        dtype, H and k those Q announces.  Returns the slope as a float."""
-        import math
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
-        if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not math.isfinite(negative_slope):
-            raise ValueError(f"{who}: negative_slope must be a finite Python number, not {negative_slope!r}")
-        if a is not None:
-            if not hasattr(a, "data_ptr") or not hasattr(a, "is_contiguous"):
-                raise ValueError(f"{who}: a must be a torch tensor or None")
-            if str(a.dtype) != dt:
-                raise ValueError(f"{who}: a has dtype {a.dtype}, the handle holds {dt}")
-            want = (int(Q.shape[1]), int(Q.shape[2])) if hasattr(Q, "dim") and Q.dim() == 3 else None  # (else _mha_args rejects Q)
-            if a.dim() != 2 or (want is not None and tuple(a.shape) != want):
-                raise ValueError(f"{who}: a must have shape (heads, k) = {want}, not {tuple(a.shape)}")
-            if not a.is_contiguous():
-                raise ValueError(f"{who}: a must be contiguous, not stride {a.stride()}")
-            if a.device.type != "cuda":
-                raise ValueError(f"{who}: a must live on the GPU, not {a.device}")
-        return float(negative_slope)
-
     def gat(self, Q, K, V, O, a=None, negative_slope=0.2, B=None, scale=1.0) -> int:
         """additive attention in ONE launch: ``mhaEdgeBias`` with the score ``scale * sum_c a[h, c] LeakyReLU(Q[i, h, c] +
         K[j, h, c]) + B[e, h]`` in the dot product's place.  GAT is k = 1 with ``a=None`` (Q = el, K = er: s = LeakyReLU(el[i] +
@@ -677,16 +630,12 @@ class anonymouslibHandle:
         operation rounded once; everything after the score is ``mha``'s.  Operands, ``B`` and ``scale`` as ``mhaEdgeBias``;
         ``negative_slope`` is a finite Python number.  Nothing of length nnz is written; THE HANDLE'S VALUES ARE NOT READ and nothing
         of the handle changes.  Anything else raises ValueError before the library is called."""
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"))
+        ins, outs = self._forward_operands(Q, K, V, O)
         scale, ldb, _ = self._mha_edge_args("gat", self._mha_heads(Q), scale, B, None, ())
         ns = self._gat_args("gat", Q, a, negative_slope)
-        heads, k, d = self._mha_args("gat", ins, (("O", O, self._m, "d"),), None)
-        for name, t in (("B", B), ("a", a)):
-            if t is not None and O.numel() and t.numel() and O.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                raise ValueError(f"gat: O shares storage with {name} (aliased)")
-        self._mha_edge_device("gat", Q, (("B", B), ("a", a)))
-        ld = self._mha_ld
-        return self.gat_ptr(heads, ns, a, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, O, ld(O))
+        heads, k, d, ld = self._operand_args("gat", 3, ins, outs, None)
+        self._after_operands("gat", Q, outs, (("B", B), ("a", a)), (("B", B), ("a", a)))
+        return self.gat_ptr(heads, ns, a, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"])
 
     def gat_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int,
                 d: int, O, ldo: int) -> int:
@@ -702,24 +651,13 @@ class anonymouslibHandle:
         ``work`` and the transposed companion; dQ, dAr and dB neither.  An output shares storage with no other argument.  The
         handle's values, the companion's included, are not read.  Anything else raises ValueError before the library is called."""
         who = "gatBackward"
-        ins = (("Q", Q, self._m, "k"), ("K", K, self._n, "k"), ("V", V, self._n, "d"), ("dO", dO, self._m, "d"))
-        outs = tuple(o for o in (("dQ", dQ, self._m, "k"), ("dK", dK, self._n, "k"), ("dV", dV, self._n, "d"),
-                                 ("dAr", dAr, self._m, "k")) if o[1] is not None)
-        others = tuple((name, t) for name, t, _, _ in ins + outs) + (("work", work), ("a", a))
-        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work, (("dAr", dAr, self._m, "k"),))
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others + (("a", a),))
         ns = self._gat_args(who, Q, a, negative_slope)
-        heads, k, d = self._mha_args(who, ins, outs, work)
-        for name, t in (("B", B), ("a", a)):
-            if t is not None:
-                for oname, o, _, _ in outs:
-                    if o.numel() and t.numel() and o.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
-                        raise ValueError(f"{who}: {oname} shares storage with {name} (aliased)")
-        self._mha_edge_device(who, Q, (("B", B), ("dB", dB), ("a", a)))
-        ld = self._mha_ld
-        return self.gat_backward_ptr(heads, ns, a, scale, B, ldb, Q, ld(Q), K, ld(K), k, V, ld(V), d, dO, ld(dO), dQ,
-                                     ld(dQ) if dQ is not None else heads * k, dK, ld(dK) if dK is not None else heads * k, dV,
-                                     ld(dV) if dV is not None else heads * d, work, dB, lddb, dAr,
-                                     ld(dAr) if dAr is not None else heads * k)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work)
+        self._after_operands(who, Q, outs, (("B", B), ("a", a)), (("B", B), ("dB", dB), ("a", a)))
+        return self.gat_backward_ptr(heads, ns, a, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"],
+                                     dK, ld["dK"], dV, ld["dV"], work, dB, lddb, dAr, ld["dAr"])
 
     def gat_backward_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
                          ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int, dAr,
@@ -735,7 +673,7 @@ class anonymouslibHandle:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless
         each is a contiguous 1-D GPU tensor of nnz values of the handle's dtype, the output shares storage with no input, and
         all live on one device"""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        dt = self._dtype_name()
         for name, t in named:
             if not hasattr(t, "data_ptr") or not hasattr(t, "is_contiguous"):
                 raise ValueError(f"{who}: {name} must be a torch tensor")
@@ -750,7 +688,7 @@ class anonymouslibHandle:
                 raise ValueError(f"{who}: {name} must be contiguous, not stride {t.stride()}")
         out_name, out = named[-1]
         for name, t in named[:-1]:
-            if out.numel() and out.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+            if _aliased(out, t):
                 raise ValueError(f"{who}: {out_name} shares storage with {name} (aliased)")
         for name, t in named:
             if t.device.type != "cuda":
@@ -786,7 +724,7 @@ class anonymouslibHandle:
         contiguous 1-D GPU tensor of the handle's dtype with nnz elements in CSR order -- the order ``inputCSR``'s value tensor
         had -- and must not share storage with that tensor (the handle keeps it in its own order).  Asynchronous on the
         handle's stream; ``val`` is only read.  Anything else raises ValueError before the library is called."""
-        dt = "torch.float64" if self._vt == _capi.F64 else "torch.float32"
+        dt = self._dtype_name()
         if not hasattr(val, "data_ptr") or not hasattr(val, "is_contiguous"):
             raise ValueError("updateValues: val must be a torch tensor")
         if self._nnz is None:
@@ -798,8 +736,7 @@ class anonymouslibHandle:
         if not val.is_contiguous():
             raise ValueError(f"updateValues: val must be contiguous, not stride {val.stride()}")
         mine = self._keep.get("val")
-        # (tensors without elements own no memory: their storages all report the same null pointer and alias nothing)
-        if val.numel() and hasattr(mine, "untyped_storage") and val.untyped_storage().data_ptr() == mine.untyped_storage().data_ptr():
+        if hasattr(mine, "data_ptr") and _aliased(val, mine):  # (inputCSR also takes raw pointers, which name no storage)
             raise ValueError("updateValues: val shares storage with the tensor given to inputCSR (aliased)")
         if val.device.type != "cuda":
             raise ValueError(f"updateValues: val must live on the GPU, not {val.device}")

@@ -1,8 +1,10 @@
-"""The nine attention entry points of the C ABI judge their arguments alike (no GPU): ONE table of the calls and their argument
-lists, and every mistake -- a null handle, a negative size, a non-finite scale, a leading dimension too small, a null operand, the
-missing companion, the CSR and the unknown format -- made in every call that has the argument, with the same code expected
-everywhere.  The per-call tests (test_attention_host.py, test_attention_backward_host.py, test_mha_host.py, test_mha_bias_host.py,
-test_mha_edge_bias_host.py, test_mha_lowp_host.py) pin each call's order on its own; this one pins that the calls agree.  Handles as
+"""The twelve attention entry points of the C ABI judge their arguments alike (no GPU): ONE table of the calls and their argument
+lists, and every mistake -- a null handle, a negative size, a non-finite scale or slope, a leading dimension too small, a null
+operand, the missing companion, the CSR and the unknown format -- made in every call that has the argument, with the same code
+expected everywhere.  The per-call tests (test_attention_host.py, test_attention_backward_host.py, test_mha_host.py,
+test_mha_bias_host.py, test_mha_edge_bias_host.py, test_mha_lowp_host.py, test_mha_lowp_backward_host.py, test_gat_host.py) pin each
+call's order on its own; this one pins that the calls agree (tests/test_attention_wrappers_host.py does the same for the Python
+wrappers).  Handles as
 test_mha_edge_bias_host.py makes them: csr5hip_create, then csr5hip_input_csr with null arrays, and fake non-null pointers --
 nothing is launched, csr5hip_get_info is the same bytes before and after."""
 import ctypes as C
@@ -29,11 +31,14 @@ ENTRIES = {
     "csr5hip_mha_edge_bias": ("handle", "heads", "scale", "B", "ldb") + _FWD,
     "csr5hip_mha_lowp": ("handle", "type", "heads", "scale", "B", "ldb") + _FWD,
     "csr5hip_mha_edge_bias_backward": ("handle", "heads", "scale", "B", "ldb") + _BWD + ("dS", "ldds"),
+    "csr5hip_mha_lowp_backward": ("handle", "type", "heads", "scale", "B", "ldb") + _BWD + ("dS", "ldds"),
+    "csr5hip_gat": ("handle", "heads", "negative_slope", "a", "scale", "B", "ldb") + _FWD,
+    "csr5hip_gat_backward": ("handle", "heads", "negative_slope", "a", "scale", "B", "ldb") + _BWD + ("dS", "ldds", "dAr", "lddar"),
 }
 BACKWARD = [name for name in ENTRIES if name.endswith("_backward")]
 # leading dimension -> (what it is a multiple of, the pointer it is judged with or None for always)
 LEADING = {"ldq": ("k", None), "ldk": ("k", None), "lddq": ("k", None), "lddk": ("k", None), "ldv": ("d", None), "ldo": ("d", None),
-           "lddo": ("d", None), "lddv": ("d", None), "ldb": (None, "B"), "ldds": (None, "dS")}
+           "lddo": ("d", None), "lddv": ("d", None), "ldb": (None, "B"), "ldds": (None, "dS"), "lddar": ("k", "dAr")}
 
 
 class Entry:
@@ -43,7 +48,8 @@ class Entry:
         self.fn, self.name, self.args = getattr(lib, name), name, ENTRIES[name]
         self.heads = HEADS if "heads" in self.args else 1
         self.good = dict(handle=handle, type=_capi.BF16, heads=self.heads, scale=0.5, slopes=FAKE, B=FAKE, ldb=self.heads, Q=FAKE, K=FAKE,
-                         V=FAKE, O=FAKE, dO=FAKE, k=K, d=D, dQ=FAKE, dK=None, dV=None, work=None, dS=None, ldds=self.heads)
+                         V=FAKE, O=FAKE, dO=FAKE, k=K, d=D, dQ=FAKE, dK=None, dV=None, work=None, dS=None, ldds=self.heads,
+                         negative_slope=0.2, a=FAKE, dAr=None)
         for ld, (width, _) in LEADING.items():
             if width:
                 self.good[ld] = self.heads * self.good[width]
@@ -88,6 +94,10 @@ def _argument_mistakes(e, fmt):
         for bad in (float("nan"), float("inf"), -float("inf")):
             assert e.call(scale=bad) == INV, (e.name, bad)
         assert e.call(scale=0.0) == fmt and e.call(scale=-3.0) == fmt, e.name
+    if e.has("negative_slope"):
+        for bad in (float("nan"), float("inf"), -float("inf")):
+            assert e.call(negative_slope=bad) == INV, (e.name, bad)
+        assert e.call(negative_slope=0.0) == fmt and e.call(negative_slope=-3.0) == fmt, e.name
     for ld, (_, pointer) in LEADING.items():
         if not e.has(ld):
             continue
@@ -119,15 +129,16 @@ def _missing_companion(e, other, **changes):
 
 
 def test_every_entry_point_is_in_the_table():
-    bound = [name for name, _, _ in _capi.SYMBOLS + _capi.SYMBOLS_BIASED + _capi.SYMBOLS_EDGE_BIAS + _capi.SYMBOLS_LOWP
-             if name.startswith(("csr5hip_attention", "csr5hip_mha"))]
-    assert sorted(bound) == sorted(ENTRIES) and len(ENTRIES) == 9
-    for name, _, argtypes in _capi.SYMBOLS + _capi.SYMBOLS_BIASED + _capi.SYMBOLS_EDGE_BIAS + _capi.SYMBOLS_LOWP:
+    lists = (_capi.SYMBOLS + _capi.SYMBOLS_BIASED + _capi.SYMBOLS_EDGE_BIAS + _capi.SYMBOLS_LOWP + _capi.SYMBOLS_LOWP_BACKWARD
+             + _capi.SYMBOLS_GAT)
+    bound = [name for name, _, _ in lists if name.startswith(("csr5hip_attention", "csr5hip_mha", "csr5hip_gat"))]
+    assert sorted(bound) == sorted(ENTRIES) and len(ENTRIES) == 12
+    for name, _, argtypes in lists:
         if name in ENTRIES:
             assert len(argtypes) == len(ENTRIES[name]), name
             for arg, ctype in zip(ENTRIES[name], argtypes):
                 integer = arg in ("type", "heads", "k", "d") or arg.startswith("ld")
-                assert ctype is (C.c_double if arg == "scale" else C.c_int if integer else C.c_void_p), (name, arg)
+                assert ctype is (C.c_double if arg in ("scale", "negative_slope") else C.c_int if integer else C.c_void_p), (name, arg)
 
 
 def test_the_same_mistake_gets_the_same_code_before_input(entries):
@@ -158,6 +169,8 @@ def test_the_same_mistake_gets_the_same_code_in_csr_format(entries):
             assert e.call(slopes=None) == CSR, e.name         # optional
         if e.has("B"):
             assert e.call(B=None) == CSR, e.name              # optional
+        if e.has("a"):
+            assert e.call(a=None) == CSR, e.name              # optional: a = 1
     for i, name in enumerate(BACKWARD):
         e, other = Entry(lib, h, name), Entry(lib, h, BACKWARD[(i + 1) % len(BACKWARD)])
         assert _missing_companion(e, other, dK=FAKE, work=FAKE) and _missing_companion(e, other, dV=FAKE, work=FAKE)
@@ -174,4 +187,6 @@ def test_the_same_mistake_gets_the_same_code_in_csr_format(entries):
         assert e.call(dQ=None, k=-1) == INV and e.call(dQ=None, ldq=e.good["ldq"] - 1) == INV, e.name
         if e.has("dS"):  # dS / dB alone is a wanted output
             assert e.call(dQ=None, dS=FAKE) == CSR and e.call(dQ=None, dS=FAKE, Q=None) == INV, e.name
+        if e.has("dAr"):  # and so is dAr
+            assert e.call(dQ=None, dAr=FAKE) == CSR and e.call(dQ=None, dAr=FAKE, Q=None) == INV, e.name
     assert _info_bytes(lib, h) == before
