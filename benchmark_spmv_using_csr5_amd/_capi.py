@@ -239,6 +239,19 @@ SYMBOLS_GAT = [
                                        C.c_int]),
 ]
 
+# the dropped attention calls and the mask, bound by load() like the others: csr5hip_mha_edge_bias's, its backward's, csr5hip_gat's and its
+# backward's arguments, each followed by p (double), seed, offset (unsigned long long) and head0; the mask: heads, p, seed, offset, head0,
+# the bytes and their row stride.  A list of their own for SYMBOLS_BIASED's reason: their declarations are in
+# include/csr5hip_dropout.h; tests/test_attention_dropout_host.py compares them with the exports.
+_DROP = [C.c_double, C.c_ulonglong, C.c_ulonglong, C.c_int]
+SYMBOLS_DROPOUT = [
+    ("csr5hip_dropout_mha", C.c_int, SYMBOLS_EDGE_BIAS[0][2] + _DROP),
+    ("csr5hip_dropout_mha_backward", C.c_int, SYMBOLS_EDGE_BIAS[1][2] + _DROP),
+    ("csr5hip_dropout_gat", C.c_int, SYMBOLS_GAT[0][2] + _DROP),
+    ("csr5hip_dropout_gat_backward", C.c_int, SYMBOLS_GAT[1][2] + _DROP),
+    ("csr5hip_dropout_mask", C.c_int, [_H, C.c_int] + _DROP + [C.c_void_p, C.c_int]),
+]
+
 _lib = None
 
 
@@ -261,7 +274,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT:
+    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT + SYMBOLS_DROPOUT:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

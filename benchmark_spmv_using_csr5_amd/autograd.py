@@ -51,8 +51,10 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from .handle import anonymouslibHandle
 
-__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention", "gat_attention"]
+__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention", "gat_attention", "dropout_attention",
+           "gat_dropout_attention"]
 
 
 def _check(rc: int, what: str) -> None:
@@ -562,3 +564,114 @@ def gat_attention(A, Q, K, V, att=None, negative_slope=0.2, scale=None, bias=Non
     if bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2):
         raise ValueError("gat_attention: bias is None or a 2-D (nnz, H) tensor in CSR order")
     return _GatAttention.apply(A, Q, K, V, att, float(negative_slope), 1.0 if scale is None else float(scale), bias)
+
+
+def _dropout_numbers(who, p, seed, offset):
+    """(p, seed, offset) as the dropped calls take them: the handle's own check (``_dropout_args``), made before anything runs"""
+    return anonymouslibHandle._dropout_args(who, p, seed, offset, 0)[:3]
+
+
+class _DropoutAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias, p, seed, offset):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        Bc = _rows_packed(bias.detach()) if bias is not None else None
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.dropoutMha(Qc, Kc, Vc, O, p, seed, offset, B=Bc, scale=scale), "dropoutMha")
+        ctx.A, ctx.scale, ctx.drop = A, scale, (p, seed, offset)
+        ctx.save_for_backward(Qc, Kc, Vc, Bc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, B = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        need_bias = B is not None and ctx.needs_input_grad[5]
+        if not (any(need) or need_bias):
+            return (None,) * 9
+        A = ctx.A
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], dO.dtype)
+        dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        p, seed, offset = ctx.drop
+        _check(A.dropoutMhaBackward(Q, K, V, dO, p, seed, offset, dQ=outs[0], dK=outs[1], dV=outs[2], work=work, B=B, scale=ctx.scale,
+                                    dB=dB), "dropoutMhaBackward")
+        return (None,) + tuple(outs) + (None, dB, None, None, None)
+
+
+def dropout_attention(A, Q, K, V, p, seed, offset=0, scale=None, bias=None, training=True):
+    """``multihead_attention`` with DROPOUT ON THE ATTENTION WEIGHTS inside the fused kernels: packed Q (m, H, k), K (n, H, k),
+    V (n, H, d) -> (m, H, d), the weights ``softmax(scale * Q K^T + bias[:, h])`` over the stored entries of row i, each dropped
+    with probability ``p`` AFTER the softmax and the kept ones scaled by 1 / (1 - p) -- ``TransformerConv(dropout=p)``'s placement.
+    ``bias`` is ``None`` or a 2-D (nnz, H) tensor in CSR order, differentiable; ``scale`` a Python float (``None`` for 1.0).
+
+    The mask is a pure function of (p, seed, offset, entry, head) -- Philox4x32-10, written out in csr5hip_dropout.h; it makes no
+    claim to match torch's generator -- so a fixed (seed, offset) makes the function deterministic, and ``A.dropoutMask``
+    reproduces it.  ``seed`` and ``offset`` are Python ints below 2**64.  DRAWING FRESH ONES PER STEP IS THE CALLER'S BUSINESS; the
+    idiom is one seed per layer and run and ``offset = step``::
+
+        out = dropout_attention(A, Q, K, V, 0.6, seed=layer_seed, offset=step, training=model.training)
+
+    ``training=False`` or ``p == 0`` is exactly ``multihead_attention(A, Q, K, V, scale=scale, bias=bias)`` -- except with a
+    ``scale`` and no bias, which that function would read as "the handle's values are the bias": that case stays on the route
+    below with p = 0, whose bits are ``A.mhaEdgeBias(B=None)``'s.  Otherwise forward is
+    ONE ``A.dropoutMha`` (one launch) and backward ONE ``A.dropoutMhaBackward`` (two launches) with the same (p, seed, offset), which
+    recompute the mask: nothing of length nnz is kept or written beside ``grad_bias`` when the bias needs one.  Buffers, the
+    companion and the workspace as ``multihead_attention``'s edge-bias route; the handle is given no values.  Nothing runs in
+    backward when nothing needs a gradient.  fp32 and fp64 handles; there is no 16-bit route."""
+    if bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2):
+        raise ValueError("dropout_attention: bias is None or a 2-D (nnz, H) tensor in CSR order")
+    p, seed, offset = _dropout_numbers("dropout_attention", p, seed, offset)
+    if (not training or p == 0.0) and (bias is not None or scale is None):
+        return multihead_attention(A, Q, K, V, scale=scale, bias=bias)
+    if not training:
+        p = 0.0  # (a scale without a bias: multihead_attention would read the handle's values as the bias; p = 0 drops nothing)
+    return _DropoutAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias, p, seed, offset)
+
+
+class _GatDropoutAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, Q, K, V, att, negative_slope, scale, bias, p, seed, offset):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        ac = att.detach().contiguous() if att is not None else None
+        Bc = _rows_packed(bias.detach()) if bias is not None else None
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.dropoutGat(Qc, Kc, Vc, O, p, seed, offset, a=ac, negative_slope=negative_slope, B=Bc, scale=scale), "dropoutGat")
+        ctx.A, ctx.ns, ctx.scale, ctx.drop = A, negative_slope, scale, (p, seed, offset)
+        ctx.save_for_backward(Qc, Kc, Vc, ac, Bc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, a, B = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        need_att = a is not None and ctx.needs_input_grad[4]
+        need_bias = B is not None and ctx.needs_input_grad[7]
+        if not (any(need) or need_att or need_bias):
+            return (None,) * 11
+        A = ctx.A
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], dO.dtype)
+        dB = torch.empty(tuple(B.shape), dtype=dO.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        dAr = torch.empty_like(Q, memory_format=torch.contiguous_format) if need_att else None  # (every row and head is written)
+        p, seed, offset = ctx.drop
+        _check(A.dropoutGatBackward(Q, K, V, dO, p, seed, offset, dQ=outs[0], dK=outs[1], dV=outs[2], work=work, a=a,
+                                    negative_slope=ctx.ns, B=B, scale=ctx.scale, dB=dB, dAr=dAr), "dropoutGatBackward")
+        grad_att = dAr.sum(0) if need_att else None  # (the kernels write the rows' shares: the reduction over the rows is torch's)
+        return (None,) + tuple(outs) + (grad_att, None, None, dB, None, None, None)
+
+
+def gat_dropout_attention(A, Q, K, V, p, seed, offset=0, att=None, negative_slope=0.2, scale=None, bias=None, training=True):
+    """``gat_attention`` with ``dropout_attention``'s dropout on the attention weights -- PyG's ``GATConv(dropout=p)`` and
+    ``GATv2Conv(dropout=p)`` recipe in the fused kernels.  The score is ``gat_attention``'s; ``p``, ``seed``, ``offset`` and the
+    mask are ``dropout_attention``'s (the idiom: ``offset = step``).  ``training=False`` or ``p == 0`` is exactly
+    ``gat_attention(A, Q, K, V, att, negative_slope, scale, bias)``.  Otherwise forward is ONE ``A.dropoutGat`` and backward ONE
+    ``A.dropoutGatBackward`` with the same (p, seed, offset); ``grad_att`` and ``grad_bias`` as ``gat_attention``'s.  Nothing runs in
+    backward when nothing needs a gradient."""
+    if bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2):
+        raise ValueError("gat_dropout_attention: bias is None or a 2-D (nnz, H) tensor in CSR order")
+    p, seed, offset = _dropout_numbers("gat_dropout_attention", p, seed, offset)
+    if not training or p == 0.0:
+        return gat_attention(A, Q, K, V, att=att, negative_slope=negative_slope, scale=scale, bias=bias)
+    return _GatDropoutAttention.apply(A, Q, K, V, att, float(negative_slope), 1.0 if scale is None else float(scale), bias, p, seed,
+                                      offset)

@@ -20,6 +20,7 @@ struct AttBwdArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's rank in the parent's CSR order)
     static constexpr bool GAT = false;  // (with EDGE: the additive score of AttBwdGatArgs in place of the dot product)
+    static constexpr bool DROP = false; // (with EDGE: the dropout mask of AttBwdDropArgs / AttBwdDropGatArgs)
     using ST = VT;                      // the type behind the operand and output pointers (AttBwdLowpArgs: another one than VT)
     int lines, k, d;     // lines: rows of the pattern walked (m in the row kernel, n in the column kernel)
     int T, sigma, tiles; // tile_elems, sigma, p - 1 of that pattern
@@ -82,6 +83,7 @@ struct AttBwdLowpArgs {
     static constexpr bool BIASED = true;
     static constexpr bool EDGE = true;
     static constexpr bool GAT = false;
+    static constexpr bool DROP = false;
     using ST = ST_;
     int lines, k, d;
     int T, sigma, tiles;
@@ -98,6 +100,22 @@ struct AttBwdLowpArgs {
     AttEdgeBiasLowpMap<ST> bias;
     ST *dS;
     int ldds;
+};
+
+// csr5hip_dropout_mha_backward (csr5_attention_bwd_drop.hip) and csr5hip_dropout_gat_backward (csr5_attention_bwd_drop_gat.hip): the
+// edge call's and the additive one's gradients under the forward's dropout mask (csr5_attention_dev.h AttDrop), recomputed per entry
+// and head from the entry's rank in the PARENT's CSR order -- the position walked in the row kernel, map[position] in the column
+// kernel.  g_e = keep ? cd : +0; dp_e = g_e * (dO_i . V_j chain), one multiplication, on both sides; p, D and ds follow from it as
+// they always do; dV's coefficient is p_e * g_e, one multiplication, in p_e's place.  The workspace keeps its meaning.
+template <typename VT>
+struct AttBwdDropArgs : AttBwdEdgeArgs<VT> {
+    static constexpr bool DROP = true;
+    AttDrop<VT> drop;
+};
+template <typename VT>
+struct AttBwdDropGatArgs : AttBwdGatArgs<VT> {
+    static constexpr bool DROP = true;
+    AttDrop<VT> drop;
 };
 
 // the arguments of head h alone: every operand moved to that head's slice, the workspace to that head's values of row 0 (biased:
@@ -125,6 +143,8 @@ __device__ __forceinline__ ARGS bwd_head(const ARGS &A, const int h)
         if (H.dAr)
             H.dAr += ok;
     }
+    if constexpr (ARGS::DROP)
+        H.drop.key.head0 += (uint32_t)h;
     if constexpr (ARGS::EDGE) {
         if (H.bias.B)
             H.bias.B += h;
@@ -151,6 +171,16 @@ __device__ __forceinline__ VT bwd_value(const ARGS &A, const int t0, const int r
         return A.bias.val[att_storage(A, t0, rem0, j)];
     else
         return (VT)0;
+}
+
+// dropout: g_e of head 0 of A of the entry of rank j of the line, keep ? cd : +0; otherwise nothing is computed
+template <typename VT, typename ARGS>
+__device__ __forceinline__ VT bwd_drop_g(const ARGS &A, const int t0, const int rem0, const int j)
+{
+    if constexpr (ARGS::DROP)
+        return att_drop_factor(A.drop, att_edge_rank(A.bias, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j), 0);
+    else
+        return (VT)1;
 }
 
 // the coefficient of dQ and dK: ds, biased t = ds * c (one rounded multiplication)
@@ -187,25 +217,29 @@ __device__ __forceinline__ VT bwd_score(const ARGS &A, const size_t i, const siz
     }
 }
 
-// s_e and dp_e of the entry (i, j); av: its value (read only when biased)
+// s_e and dp_e of the entry (i, j); av: its value (read only when biased); g: its dropout factor (used only with ARGS::DROP)
 template <typename VT, bool VEC, typename ARGS>
-__device__ __forceinline__ void bwd_entry(const ARGS &A, const size_t i, const size_t j, const VT av, VT &s, VT &dp)
+__device__ __forceinline__ void bwd_entry(const ARGS &A, const size_t i, const size_t j, const VT av, const VT g, VT &s, VT &dp)
 {
     s = bwd_score<VT, VEC>(A, i, j, av);
     dp = att_score<VT, VEC>(A.dO + i * A.lddo, A.V + j * A.ldv, A.d);
+    if constexpr (ARGS::DROP)
+        dp = g * dp;
 }
 
 // p_e and ds_e (biased: t_e = ds_e * c, dK's coefficient) of the entry (i, j) from the workspace values of row i: the column
-// kernel's entry
+// kernel's entry.  With ARGS::DROP p leaves as dV's coefficient, p_e * g
 template <typename VT, bool VEC, typename ARGS>
-__device__ __forceinline__ void bwd_entry_col(const ARGS &A, const size_t i, const size_t j, const VT av, VT &p, VT &ds)
+__device__ __forceinline__ void bwd_entry_col(const ARGS &A, const size_t i, const size_t j, const VT av, const VT g, VT &p, VT &ds)
 {
     const VT *wk = A.work + (size_t)A.ws * i;
     const VT M = wk[0], r = wk[1], D = wk[2];
     VT s, dp;
-    bwd_entry<VT, VEC>(A, i, j, av, s, dp);
+    bwd_entry<VT, VEC>(A, i, j, av, g, s, dp);
     p = exp_vt(s - M) * r;
     ds = bwd_coef(A, p * (dp - D));
+    if constexpr (ARGS::DROP)
+        p = p * g;
 }
 
 // ---- accumulation, L <= 16: ONE chain per output column over the entries in ascending order.  coef / idx: lane sub * 16 + e
@@ -509,10 +543,14 @@ __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, 
             if constexpr (ARGS::EDGE)
                 if (act)
                     av = att_edge_value(A.bias, er, 0);
+            VT g = (VT)1;
+            if constexpr (ARGS::DROP)
+                if (act)
+                    g = att_drop_factor(A.drop, er, 0);
             if constexpr (COL) {
                 VT p = (VT)0, ds = (VT)0;
                 if (act)
-                    bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, av, p, ds);
+                    bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)other, r, av, g, p, ds);
                 if (A.dV)
                     bwd_short_acc<VT>(rowok, rl, sub, pos, p, other, A.dO, A.lddo, A.d, A.dV + r * A.lddv);
                 if constexpr (ARGS::GAT) {
@@ -524,7 +562,7 @@ __device__ __forceinline__ void bwd_short(const ARGS &A0, const long long row0, 
             } else {
                 VT s = neg_inf<VT>(), dp = (VT)0;
                 if (act)
-                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, av, s, dp);
+                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)other, av, g, s, dp);
                 const VT mx = group_max<G>(s);
                 const VT w = act ? exp_vt(s - mx) : (VT)0;
                 const VT rinv = (VT)1 / group_sum<G>(w);
@@ -564,7 +602,7 @@ __device__ __forceinline__ void bwd_wave_head(const ARGS &A, const bool first, c
             const int i = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             const VT av = bwd_value<VT>(A, t0, rem0, j);
             VT p, ds;
-            bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, av, p, ds);
+            bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, av, bwd_drop_g<VT>(A, t0, rem0, j), p, ds);
             a[j] = p;
             b[j] = ds;
             cl[j] = i;
@@ -584,7 +622,7 @@ __device__ __forceinline__ void bwd_wave_head(const ARGS &A, const bool first, c
             const int cj = first ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             const VT av = bwd_value<VT>(A, t0, rem0, j);
             VT s, dp;
-            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, s, dp);
+            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, bwd_drop_g<VT>(A, t0, rem0, j), s, dp);
             a[j] = s;
             b[j] = dp;
             cl[j] = cj;
@@ -651,7 +689,7 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
                 const int i = first || !staged ? A.col[att_storage(A, t0, rem0, base + jj)] : cl[jj];
                 const VT av = bwd_value<VT>(A, t0, rem0, base + jj);
                 VT p, ds;
-                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, av, p, ds);
+                bwd_entry_col<VT, VEC>(A, (size_t)(uint32_t)i, r, av, bwd_drop_g<VT>(A, t0, rem0, base + jj), p, ds);
                 a[jj] = p;
                 b[jj] = ds;
                 cl[jj] = i;
@@ -673,7 +711,7 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
             const int cj = first || !staged ? A.col[att_storage(A, t0, rem0, j)] : cl[j];
             const VT av = bwd_value<VT>(A, t0, rem0, j);
             VT s, dp;
-            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, s, dp);
+            bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, bwd_drop_g<VT>(A, t0, rem0, j), s, dp);
             if (staged) {
                 a[j] = s;
                 b[j] = dp;
@@ -708,7 +746,7 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
                 const int cj = A.col[att_storage(A, t0, rem0, j)];
                 const VT av = bwd_value<VT>(A, t0, rem0, j);
                 VT s;
-                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, s, dp);
+                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, bwd_drop_g<VT>(A, t0, rem0, j), s, dp);
                 w = exp_vt(s - mx);
             }
             const VT p = w * rinv;
@@ -730,7 +768,7 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
                     const int cj = A.col[att_storage(A, t0, rem0, j)];
                     const VT av = bwd_value<VT>(A, t0, rem0, j);
                     VT s, dp;
-                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, s, dp);
+                    bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, bwd_drop_g<VT>(A, t0, rem0, j), s, dp);
                     const VT p = exp_vt(s - mx) * rinv;
                     bwd_store_ds(A, t0, rem0, j, p * (dp - D));
                 }
@@ -746,7 +784,7 @@ __device__ __forceinline__ void bwd_hub_head(const ARGS &A, const bool first, co
                 const int cj = A.col[att_storage(A, t0, rem0, base + jj)];
                 const VT av = bwd_value<VT>(A, t0, rem0, base + jj);
                 VT s, dp;
-                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, s, dp);
+                bwd_entry<VT, VEC>(A, r, (size_t)(uint32_t)cj, av, bwd_drop_g<VT>(A, t0, rem0, base + jj), s, dp);
                 const VT p = exp_vt(s - mx) * rinv;
                 a[jj] = bwd_coef(A, p * (dp - D));
                 cl[jj] = cj;
@@ -855,6 +893,18 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_gat(const AttBwdGatA
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }
 
+// the dropped calls: the edge call's and the additive one's kernels on their derived argument structs
+template <typename VT, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_drop(const AttBwdDropArgs<VT> A)
+{
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+template <typename VT, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_bwd_drop_gat(const AttBwdDropGatArgs<VT> A)
+{
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+
 // 16-bit operands and outputs, float arithmetic: always the packed, edge-biased call.  6 waves per SIMD are
 // k_attention_bwd_edge<float, ..>'s: left to itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 81
 // (row kernel) and 82 (column kernel) registers with 16-byte loads, which are 5 waves
@@ -890,6 +940,16 @@ template <bool VEC, bool COL, bool MH, typename VT>
 static void attention_bwd_enqueue(const AttBwdGatArgs<VT> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_bwd_gat<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdDropArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_drop<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename VT>
+static void attention_bwd_enqueue(const AttBwdDropGatArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_drop_gat<VT, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 
 template <bool VEC, bool COL, bool MH, typename ST>
@@ -993,6 +1053,8 @@ hipError_t attention_bwd_launch(const Geometry &g, const DeviceArrays &d, const 
         att_set_gat(A.gat, c);
         dAr = c.k > 0 ? c.dAr : nullptr;
     }
+    if constexpr (ARGS::DROP)
+        att_set_drop(A.drop, c);
     const bool column = c.gt && c.dt && (!ARGS::EDGE || c.map) && (c.dK || c.dV);
     hipError_t e = hipSuccess;
     if (c.dQ || dS || column || dAr) {

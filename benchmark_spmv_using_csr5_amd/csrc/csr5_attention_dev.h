@@ -247,6 +247,78 @@ static void att_set_gat(AttGat<VT> &g, const AttCall &c)
     g.ns = (VT)c.negative_slope;
 }
 
+// The dropout mask of the dropped entry points (csr5hip_dropout.h; csr5_attention_drop.hip, csr5_attention_drop_gat.hip and their
+// backwards): a pure function of (seed, offset, entry, head), so that the forward and both backward kernels recompute the same bits
+// and nothing of length nnz is kept.  It rides NEXT TO an AttEdgeBias, whose map gives the column kernel the entry's rank.
+//     counter = (e, g >> 2, offset low, offset high)    e: the entry's rank in the PARENT's CSR order, g = head0 + h
+//     key     = (seed low, seed high)
+//     dropped = philox4x32_10(counter, key)[g & 3] < thr
+// thr = min(llrint(p 2^32), 2^32 - 1), cd = (VT)(1 / (1 - p)): formed once on the host (att_set_drop).  thr = 0 drops nothing.
+struct AttDropKey {
+    uint32_t thr;
+    uint32_t seed_lo, seed_hi;
+    uint32_t off_lo, off_hi;
+    uint32_t head0; // the absolute head of head 0 of the operands (bwd_head moves it along with the slices); unsigned: no sum of it
+                    // and a head index overflows (the host admits head0 + heads <= INT_MAX)
+};
+template <typename VT>
+struct AttDrop {
+    AttDropKey key;
+    VT cd;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11), the word w of the block of (c0, c1, c2, c3) under (k0, k1)
+__host__ __device__ __forceinline__ uint32_t att_philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                             uint32_t k1, const int w)
+{
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
+}
+
+// whether head h (of the operands as K holds them) of the entry of rank e is kept
+__host__ __device__ __forceinline__ bool att_drop_keep(const AttDropKey &K, const size_t e, const int h)
+{
+    const uint32_t g = K.head0 + (uint32_t)h;
+    return att_philox_word((uint32_t)e, g >> 2, K.off_lo, K.off_hi, K.seed_lo, K.seed_hi, (int)(g & 3u)) >= K.thr;
+}
+
+// the factor of a kept weight in the backward: g_e = keep ? cd : +0
+template <typename VT>
+__device__ __forceinline__ VT att_drop_factor(const AttDrop<VT> &D, const size_t e, const int h)
+{
+    return att_drop_keep(D.key, e, h) ? D.cd : (VT)0;
+}
+
+inline AttDropKey att_drop_key(const AttCall &c)
+{
+    AttDropKey k;
+    const long long t = llrint(c.p * 4294967296.0);
+    k.thr = (uint32_t)(t < 0 ? 0 : t > 4294967295ll ? 4294967295ll : t);
+    k.seed_lo = (uint32_t)c.seed;
+    k.seed_hi = (uint32_t)(c.seed >> 32);
+    k.off_lo = (uint32_t)c.offset;
+    k.off_hi = (uint32_t)(c.offset >> 32);
+    k.head0 = (uint32_t)c.head0;
+    return k;
+}
+
+template <typename VT>
+static void att_set_drop(AttDrop<VT> &d, const AttCall &c)
+{
+    d.key = att_drop_key(c);
+    d.cd = (VT)(1.0 / (1.0 - c.p));
+}
+
 // The variant-specific part of a launch, forward and backward alike: the bias fields from the call.  side: the arrays of the pattern
 // the kernel walks (the parent's, or the companion's in the column kernel); map: null where that pattern is the parent's, the
 // companion's source map in the column kernel.

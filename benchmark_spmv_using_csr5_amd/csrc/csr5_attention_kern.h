@@ -21,6 +21,7 @@ struct AttArgs {
     static constexpr bool BIASED = false;
     static constexpr bool EDGE = false; // (with BIASED: the bias is AttEdgeBias, read at the entry's CSR rank)
     static constexpr bool GAT = false;  // (with EDGE: the additive score of AttGatArgs in place of the dot product)
+    static constexpr bool DROP = false; // (with EDGE: the dropout mask of AttDropArgs / AttDropGatArgs on the weights)
     using ST = VT;                      // the type Q, K, V and O are stored in (AttLowpArgs: another one than the arithmetic's)
     int m, k, d;
     int heads, hper;     // heads of the packed operands; heads of one workgroup (blockIdx.y owns heads y hper .. y hper + hper - 1)
@@ -57,6 +58,28 @@ struct AttGatArgs : AttEdgeArgs<VT> {
     AttGat<VT> gat;
 };
 
+// csr5hip_dropout_mha (csr5_attention_drop.hip) and csr5hip_dropout_gat (csr5_attention_drop_gat.hip): the edge call and the additive
+// one with a seeded dropout mask on the weights (csr5_attention_dev.h AttDrop).  M, w and Z are the undropped call's -- the softmax is
+// over all stored entries --; the weight that enters the product is keep ? w : +0, and the row's factor is rinv * cd, one
+// multiplication per row and head.  With thr = 0 and cd = 1 every bit is the undropped call's.
+template <typename VT>
+struct AttDropArgs : AttEdgeArgs<VT> {
+    static constexpr bool DROP = true;
+    AttDrop<VT> drop;
+};
+template <typename VT>
+struct AttDropGatArgs : AttGatArgs<VT> {
+    static constexpr bool DROP = true;
+    AttDrop<VT> drop;
+};
+
+// the weight of head h of the entry of rank e that enters the product: w, dropped +0
+template <typename VT, typename ARGS>
+__device__ __forceinline__ VT att_dropped(const ARGS &A, const size_t e, const int h, const VT w)
+{
+    return att_drop_keep(A.drop.key, e, h) ? w : (VT)0;
+}
+
 // the additive score's z of an entry of head h: att_gat_z on that head's k values of a
 template <typename VT, typename ARGS>
 __device__ __forceinline__ VT att_gat_chain(const ARGS &A, const int h, const VT *q, const VT *kr)
@@ -73,6 +96,7 @@ struct AttLowpArgs {
     static constexpr bool BIASED = true;
     static constexpr bool EDGE = true;
     static constexpr bool GAT = false;
+    static constexpr bool DROP = false;
     using ST = ST_;
     int m, k, d;
     int heads, hper;
@@ -137,8 +161,12 @@ __device__ __forceinline__ void att_short(const ARGS &A, const long long row0, c
                     s = att_bias_score(A.bias, h, s, av);
             }
             const VT mx = group_max<G>(s);
-            const VT w = act ? exp_vt(s - mx) : (VT)0;
-            const VT rinv = (VT)1 / group_sum<G>(w);
+            VT w = act ? exp_vt(s - mx) : (VT)0;
+            VT rinv = (VT)1 / group_sum<G>(w);
+            if constexpr (ARGS::DROP) { // (after Z: the softmax is over all stored entries)
+                w = act ? att_dropped(A, er, h, w) : (VT)0;
+                rinv = rinv * A.drop.cd;
+            }
             for (int cb = 0; cb < A.d; cb += G) { // (uniform)
                 const int c = cb + pos;
                 VT acc = (VT)0;
@@ -191,10 +219,15 @@ __device__ __forceinline__ void att_wave_row(const ARGS &A, const size_t r, cons
         VT z = (VT)0;
         for (int j = lane; j < rl; j += OMEGA) { // (a lane reads back what it stored itself)
             const VT w = exp_vt(sc[j] - mx);
-            sc[j] = w;
+            if constexpr (ARGS::DROP)
+                sc[j] = att_dropped(A, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h, w);
+            else
+                sc[j] = w;
             z += w;
         }
-        const VT rinv = (VT)1 / wave_sum(z);
+        VT rinv = (VT)1 / wave_sum(z);
+        if constexpr (ARGS::DROP)
+            rinv = rinv * A.drop.cd;
         att_wave_sync();
         for (int cb = 0; cb < A.d; cb += OMEGA) {
             const int wb = A.d - cb < OMEGA ? A.d - cb : OMEGA;
@@ -255,7 +288,10 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const t
     if (staged) {
         for (int j = tid; j < rl; j += AT_BLOCK) { // (a lane reads back what it stored itself)
             const VT w = exp_vt(sc[j] - mx);
-            sc[j] = w;
+            if constexpr (ARGS::DROP)
+                sc[j] = att_dropped(A, (size_t)t0 * A.T + (size_t)rem0 + (size_t)j, h, w);
+            else
+                sc[j] = w;
             z += w;
         }
     }
@@ -283,7 +319,10 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const t
                     else if constexpr (ARGS::BIASED)
                         s = att_bias_score(A.bias, h, s, A.bias.val[st]);
                     const VT w = exp_vt(s - mx);
-                    sc[jj] = w;
+                    if constexpr (ARGS::DROP)
+                        sc[jj] = att_dropped(A, (size_t)t0 * A.T + (size_t)rem0 + (size_t)(base + jj), h, w);
+                    else
+                        sc[jj] = w;
                     cl[jj] = cj;
                     if (cg == 0)
                         z += w;
@@ -308,8 +347,11 @@ __device__ __forceinline__ void att_hub_head(const ARGS &A, const int h, const t
                 }
             }
         }
-        if (cg == 0)
+        if (cg == 0) {
             rinv = (VT)1 / block_combine<VT, false>(wave_sum(z), red4);
+            if constexpr (ARGS::DROP)
+                rinv = rinv * A.drop.cd;
+        }
 #pragma unroll
         for (int b = 0; b < AT_HUB_BLOCKS; b++) {
             const int cb = cg + b * OMEGA;
@@ -422,6 +464,19 @@ __global__ void __launch_bounds__(AT_BLOCK) k_attention_gat(const AttGatArgs<VT>
     CSR5_ATTENTION_KERNEL_BODY(true)
 }
 
+// the dropped calls: the edge call's and the additive one's kernels on their derived argument structs
+template <typename VT, bool VEC>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_drop(const AttDropArgs<VT> A)
+{
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+template <typename VT>
+__global__ void __launch_bounds__(AT_BLOCK) k_attention_drop_gat(const AttDropGatArgs<VT> A)
+{
+    constexpr bool VEC = false;
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+
 // 16-bit operands, float arithmetic: always the packed, edge-biased call.  7 waves per SIMD are k_attention_edge<float, ..>'s: left to
 // itself the compiler widens a whole 32-byte block of bf16 ahead of the chain and takes 75 registers (6 waves)
 #if defined(__HIP__)
@@ -457,6 +512,16 @@ template <bool VEC, bool MH, typename VT>
 static void attention_enqueue(const AttGatArgs<VT> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_gat<VT>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttDropArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_drop<VT, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename VT>
+static void attention_enqueue(const AttDropGatArgs<VT> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_drop_gat<VT>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 template <bool VEC, bool MH, typename ST>
 static void attention_enqueue(const AttLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
@@ -513,6 +578,8 @@ hipError_t attention_launch(const Geometry &g, const DeviceArrays &d, const AttC
         att_set_bias(A.bias, d, nullptr, c);
     if constexpr (ARGS::GAT)
         att_set_gat(A.gat, c);
+    if constexpr (ARGS::DROP)
+        att_set_drop(A.drop, c);
     bool vec = false; // (the additive score takes element loads: one kernel, whatever the alignment of Q and K)
     if constexpr (!ARGS::GAT)
         vec = attention_vec<ST>(c.heads, c.Q, c.ldq, c.K, c.ldk, c.k);

@@ -9,6 +9,7 @@
 // This unit: create / free, options, setX, the entry points, graphs, info and the device shims.  The conversion lives in
 // csr5_convert.hip, the checkpoint in csr5_checkpoint.hip, the column-slab build in csr5_slab_build.hip; csr5_handle.h has the handle.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -488,8 +489,15 @@ int csr5hip_row_softmax_grad(csr5hip_handle h, const void *d_p_csr, const void *
     return CSR5HIP_SUCCESS;
 }
 
+// the dropout fields of a call (p = 0 and head0 = 0 where the call has none): p finite with 0 <= p < 1, head0 >= 0, and every absolute
+// head head0 + h an int
+static bool att_drop_ok(const AttCall &c)
+{
+    return std::isfinite(c.p) && c.p >= 0.0 && c.p < 1.0 && c.head0 >= 0 && (long long)c.head0 + (long long)c.heads <= (long long)INT_MAX;
+}
+
 // ---- attention on the pattern (csr5_attention*.hip) ---------------------------------------------------------------------------
-// The twelve entry points fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
+// The twelve entry points, and the four dropped ones further down, fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
 // trivial cases, the launch.  The single-head calls are heads = 1.  The forward reads row_ptr, tile_ptr and the tile-ordered
 // column_index of the parent, whatever path spmv() takes (biased: its tile-ordered values too); it allocates nothing and changes
 // nothing: enqueue-only.  lowp: the call names the type its operands are stored in (operand_type, judged here); the others take the handle's.
@@ -499,7 +507,7 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
         return CSR5HIP_INVALID_ARGUMENT;
     if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
         return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
-    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope))
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope) || !att_drop_ok(c))
         return CSR5HIP_INVALID_ARGUMENT;
     const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
     if (c.ldq < wk || c.ldk < wk || c.ldv < wd || c.ldo < wd || (c.B && c.ldb < c.heads))
@@ -523,6 +531,10 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
         HIP_TRY(launch_mha_biased(h->g, h->d, h->value_type, c, h->stream));
     else if (variant == ATT_GAT)
         HIP_TRY(launch_gat(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_DROP)
+        HIP_TRY(launch_mha_drop(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_DROP_GAT)
+        HIP_TRY(launch_gat_drop(h->g, h->d, h->value_type, c, h->stream));
     else
         HIP_TRY(launch_mha_edge(h->g, h->d, h->value_type, c, h->stream));
     return CSR5HIP_SUCCESS;
@@ -539,7 +551,7 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         return CSR5HIP_INVALID_ARGUMENT;
     if (lowp && operand_type != CSR5HIP_BF16 && operand_type != CSR5HIP_F16)
         return CSR5HIP_UNSUPPORTED_VALUE_TYPE;
-    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope))
+    if (c.heads < 0 || c.k < 0 || c.d < 0 || !std::isfinite(c.scale) || !std::isfinite(c.negative_slope) || !att_drop_ok(c))
         return CSR5HIP_INVALID_ARGUMENT;
     const long long wk = (long long)c.heads * c.k, wd = (long long)c.heads * c.d;
     if (c.ldq < wk || c.ldk < wk || c.lddq < wk || c.lddk < wk || c.ldv < wd || c.lddo < wd || c.lddv < wd ||
@@ -562,7 +574,7 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         return CSR5HIP_SUCCESS;
     const size_t vs = lowp ? 2 : h->vsize(); // (lowp: the word 0x0000 is +0 in both 16-bit types)
     // no entries (and then no companion arrays, and no element of dS / dB): the zeros
-    const bool mapped = variant == ATT_EDGE || variant == ATT_GAT; // the column kernel finds B's element through the source map
+    const bool mapped = variant != ATT_PLAIN && variant != ATT_BIASED; // the column kernel finds B's element through the source map
     if (nnz == 0 || (column && (!h->comp.at || (mapped && !h->comp[A_MAP].ptr)))) {
         if (c.dQ && c.k > 0 && h->g.m > 0)
             HIP_TRY(hipMemset2DAsync(c.dQ, (size_t)c.lddq * vs, 0, (size_t)wk * vs, (size_t)h->g.m, h->stream));
@@ -587,6 +599,10 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         HIP_TRY(launch_mha_biased_bwd(h->g, h->d, h->value_type, c, h->stream));
     else if (variant == ATT_GAT)
         HIP_TRY(launch_gat_bwd(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_DROP)
+        HIP_TRY(launch_mha_drop_bwd(h->g, h->d, h->value_type, c, h->stream));
+    else if (variant == ATT_DROP_GAT)
+        HIP_TRY(launch_gat_drop_bwd(h->g, h->d, h->value_type, c, h->stream));
     else
         HIP_TRY(launch_mha_edge_bwd(h->g, h->d, h->value_type, c, h->stream));
     return CSR5HIP_SUCCESS;
@@ -715,6 +731,78 @@ int csr5hip_gat_backward(csr5hip_handle h, int heads, double negative_slope, con
     c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb; c.a = d_a; c.negative_slope = negative_slope;
     c.dAr = d_dAr; c.lddar = lddar;
     return attention_backward(h, "csr5hip_gat_backward", ATT_GAT, false, 0, c);
+}
+
+// the dropped calls (csr5hip_dropout.h): the edge call's and the additive one's descriptors with the mask's fields; the shared paths
+// above judge them and launch the dropped kernels
+static void att_set_dropout(AttCall &c, double p, unsigned long long seed, unsigned long long offset, int head0)
+{
+    c.p = p; c.seed = seed; c.offset = offset; c.head0 = head0;
+}
+
+int csr5hip_dropout_mha(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq, const void *d_K,
+                        int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo, double p, unsigned long long seed,
+                        unsigned long long offset, int head0)
+{
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_forward(h, ATT_DROP, false, 0, c);
+}
+
+int csr5hip_dropout_mha_backward(csr5hip_handle h, int heads, double scale, const void *d_B, int ldb, const void *d_Q, int ldq,
+                                 const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, const void *d_dO, int lddo,
+                                 void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv, void *d_work, void *d_dB, int lddb,
+                                 double p, unsigned long long seed, unsigned long long offset, int head0)
+{
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_backward(h, "csr5hip_dropout_mha_backward", ATT_DROP, false, 0, c);
+}
+
+int csr5hip_dropout_gat(csr5hip_handle h, int heads, double negative_slope, const void *d_a, double scale, const void *d_B, int ldb,
+                        const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo,
+                        double p, unsigned long long seed, unsigned long long offset, int head0)
+{
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.a = d_a; c.negative_slope = negative_slope;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_forward(h, ATT_DROP_GAT, false, 0, c);
+}
+
+int csr5hip_dropout_gat_backward(csr5hip_handle h, int heads, double negative_slope, const void *d_a, double scale, const void *d_B,
+                                 int ldb, const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
+                                 const void *d_dO, int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv,
+                                 void *d_work, void *d_dB, int lddb, void *d_dAr, int lddar, double p, unsigned long long seed,
+                                 unsigned long long offset, int head0)
+{
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb; c.a = d_a; c.negative_slope = negative_slope;
+    c.dAr = d_dAr; c.lddar = lddar;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_backward(h, "csr5hip_dropout_gat_backward", ATT_DROP_GAT, false, 0, c);
+}
+
+// the mask itself: it needs only nnz, so CSR and CSR5 format are served alike; enqueue-only
+int csr5hip_dropout_mask(csr5hip_handle h, int heads, double p, unsigned long long seed, unsigned long long offset, int head0,
+                         void *d_mask, int ldm)
+{
+    AttCall c{};
+    c.heads = heads;
+    att_set_dropout(c, p, seed, offset, head0);
+    if (!h || heads < 0 || !att_drop_ok(c) || ldm < heads)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const bool loaded = h->format == CSR5HIP_FORMAT_CSR || h->format == CSR5HIP_FORMAT_CSR5;
+    const int nnz = loaded ? h->g.nnz : 0;
+    if (nnz > 0 && heads > 0 && !d_mask)
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (!loaded)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (nnz == 0 || heads == 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_dropout_mask(nnz, c, (unsigned char *)d_mask, ldm, h->stream));
+    return CSR5HIP_SUCCESS;
 }
 
 // ---- new values under an unchanged pattern (csr5_refresh.hip) ---------------------------------------------------------------

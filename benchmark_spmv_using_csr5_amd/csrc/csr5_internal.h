@@ -267,6 +267,9 @@ struct AttCall {
     int ldb;
     const void *a;         // gat: the attention vector, heads x k contiguous device values, or null (a = 1)
     double negative_slope; // gat: the slope of the LeakyReLU for u <= 0, converted once to the value type
+    double p;              // dropout: the probability that a weight is dropped, 0 <= p < 1 (0 in every other call)
+    unsigned long long seed, offset; // dropout: the mask's key and the high counter words (csr5_attention_dev.h AttDropKey)
+    int head0;             // dropout: the absolute head of the operands' head 0
 };
 // One call of the backward: the forward's operands, the gradient of O, the wanted outputs (null: not wanted; EVERY row of a wanted
 // one is written in its heads k / heads d columns) and the transposed companion the column kernel walks (gt, dt; edge: and its source
@@ -290,7 +293,7 @@ struct AttBwdCall : AttCall {
     const DeviceArrays *dt;
     const uint32_t *map;
 };
-enum AttVariant { ATT_PLAIN, ATT_BIASED, ATT_EDGE, ATT_GAT };
+enum AttVariant { ATT_PLAIN, ATT_BIASED, ATT_EDGE, ATT_GAT, ATT_DROP, ATT_DROP_GAT };
 // the type of the launcher templates' instantiations (attention_launch, attention_bwd_launch), one per unit and operand type
 using AttLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttCall &, hipStream_t);
 using AttBwdLaunch = hipError_t(const Geometry &, const DeviceArrays &, const AttBwdCall &, hipStream_t);
@@ -321,6 +324,14 @@ hipError_t launch_gat_bwd(const Geometry &g, const DeviceArrays &d, int value_ty
 // the caller; B, Q, K, V, dO and dQ, dK, dV, dS all of that type, leading dimensions in its elements), float arithmetic, every output
 // rounded once; c.work is FLOAT, 4 m heads values.  Neither d.val nor c.dt->val is read
 hipError_t launch_mha_lowp_bwd(const Geometry &g, const DeviceArrays &d, int operand_type, const AttBwdCall &c, hipStream_t s);
+// csr5_attention_drop.hip, csr5_attention_drop_gat.hip and their backwards: launch_mha_edge, launch_gat and their gradients with a seeded
+// dropout mask on the weights after the softmax (c.p, c.seed, c.offset, c.head0); launch_dropout_mask writes the mask itself, one byte
+// (1 kept, 0 dropped) per entry e < nnz and head h < c.heads at mask[e * ldm + h]
+hipError_t launch_mha_drop(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
+hipError_t launch_gat_drop(const Geometry &g, const DeviceArrays &d, int value_type, const AttCall &c, hipStream_t s);
+hipError_t launch_mha_drop_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+hipError_t launch_gat_drop_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
+hipError_t launch_dropout_mask(int nnz, const AttCall &c, unsigned char *mask, int ldm, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

@@ -668,6 +668,143 @@ class anonymouslibHandle:
                                               int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
                                               _ptr(dB), int(lddb), _ptr(dAr), int(lddar))
 
+    # -- dropout on the attention weights: a seeded mask inside the mha and gat kernels (csr5hip_dropout.h) ----------------------
+    @staticmethod
+    def _dropout_args(who: str, p, seed, offset, head0):
+        """the checks of the mask's arguments, made before everything else of the call: ValueError unless p is a Python number with
+        0 <= p < 1, seed and offset are Python ints in [0, 2**64) and head0 is a Python int >= 0 (bools are none of these).
+        Returns (p, seed, offset, head0)."""
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not math.isfinite(p) or not 0.0 <= p < 1.0:
+            raise ValueError(f"{who}: p must be a Python number with 0 <= p < 1, not {p!r}")
+        for name, x in (("seed", seed), ("offset", offset)):
+            if isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < 2 ** 64:
+                raise ValueError(f"{who}: {name} must be a Python int in [0, 2**64), not {x!r}")
+        if isinstance(head0, bool) or not isinstance(head0, int) or not 0 <= head0 < 2 ** 31:
+            raise ValueError(f"{who}: head0 must be a Python int in [0, 2**31), not {head0!r}")
+        return float(p), seed, offset, head0
+
+    def dropoutMha(self, Q, K, V, O, p, seed, offset=0, head0=0, B=None, scale=1.0) -> int:
+        """``mhaEdgeBias`` (``B=None``: no bias) with DROPOUT ON THE ATTENTION WEIGHTS in the same ONE launch: the softmax is over
+        all stored entries, a weight is dropped with probability ``p`` (0 <= p < 1) after it, and the kept ones are scaled by
+        1 / (1 - p).  The mask is a pure function of (p, seed, offset, entry's CSR rank, head0 + h) -- Philox4x32-10, written out
+        in csr5hip_dropout.h and restated by ``dropoutMask`` -- so the same (seed, offset) gives the same bits, and ``offset = step``
+        gives a fresh mask per step.  ``seed`` and ``offset`` are Python ints below 2**64; ``head0`` is the absolute head of
+        Q[:, 0]: head h of a packed call is the H = 1 call with ``head0 + h`` on that head's slices.  With p = 0 every bit is
+        ``mhaEdgeBias``'s.  Operands, ``B`` and ``scale`` as ``mhaEdgeBias``; nothing of length nnz is written and nothing of the
+        handle changes.  Anything else raises ValueError before the library is called."""
+        who = "dropoutMha"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ins, outs = self._forward_operands(Q, K, V, O)
+        scale, ldb, _ = self._mha_edge_args(who, self._mha_heads(Q), scale, B, None, ())
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, None)
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B),))
+        return self.dropout_mha_ptr(heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"], p, seed, offset, head0)
+
+    def dropout_mha_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int, O,
+                        ldo: int, p: float, seed: int, offset: int, head0: int) -> int:
+        """csr5hip_dropout_mha on raw device pointers (or tensors); B None for no bias"""
+        return self._lib.csr5hip_dropout_mha(self._h, int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq), _ptr(K),
+                                             int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo), float(p), int(seed),
+                                             int(offset), int(head0))
+
+    def dropoutMhaBackward(self, Q, K, V, dO, p, seed, offset=0, head0=0, dQ=None, dK=None, dV=None, work=None, B=None, scale=1.0,
+                           dB=None) -> int:
+        """the gradients of ``dropoutMha`` in TWO launches, for the same (p, seed, offset, head0): both kernels recompute the
+        forward's mask.  Operands, outputs, ``work``, ``B``, ``scale`` and ``dB`` as ``mhaEdgeBiasBackward``.  With p = 0 every bit
+        is that call's.  Anything else raises ValueError before the library is called."""
+        who = "dropoutMhaBackward"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work)
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B), ("dB", dB)))
+        return self.dropout_mha_backward_ptr(heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ, ld["dQ"],
+                                             dK, ld["dK"], dV, ld["dV"], work, dB, lddb, p, seed, offset, head0)
+
+    def dropout_mha_backward_ptr(self, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V, ldv: int, d: int,
+                                 dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB, lddb: int, p: float, seed: int,
+                                 offset: int, head0: int) -> int:
+        """csr5hip_dropout_mha_backward on raw device pointers (or tensors); None for B or for an output that is not wanted"""
+        return self._lib.csr5hip_dropout_mha_backward(self._h, int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q), int(ldq),
+                                                      _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(dO), int(lddo),
+                                                      _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
+                                                      _ptr(dB), int(lddb), float(p), int(seed), int(offset), int(head0))
+
+    def dropoutGat(self, Q, K, V, O, p, seed, offset=0, head0=0, a=None, negative_slope=0.2, B=None, scale=1.0) -> int:
+        """``gat`` with ``dropoutMha``'s dropout on the attention weights, in ONE launch -- PyG's ``GATConv(dropout=p)`` recipe.  The
+        score is ``gat``'s, bit for bit; the mask and everything after the score are ``dropoutMha``'s.  With p = 0 every bit is
+        ``gat``'s.  Anything else raises ValueError before the library is called."""
+        who = "dropoutGat"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ins, outs = self._forward_operands(Q, K, V, O)
+        scale, ldb, _ = self._mha_edge_args(who, self._mha_heads(Q), scale, B, None, ())
+        ns = self._gat_args(who, Q, a, negative_slope)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, None)
+        self._after_operands(who, Q, outs, (("B", B), ("a", a)), (("B", B), ("a", a)))
+        return self.dropout_gat_ptr(heads, ns, a, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"], p, seed, offset,
+                                    head0)
+
+    def dropout_gat_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
+                        ldv: int, d: int, O, ldo: int, p: float, seed: int, offset: int, head0: int) -> int:
+        """csr5hip_dropout_gat on raw device pointers (or tensors); a None for a = 1, B None for no bias"""
+        return self._lib.csr5hip_dropout_gat(self._h, int(heads), float(negative_slope), _ptr(a), float(scale), _ptr(B), int(ldb),
+                                             _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O),
+                                             int(ldo), float(p), int(seed), int(offset), int(head0))
+
+    def dropoutGatBackward(self, Q, K, V, dO, p, seed, offset=0, head0=0, dQ=None, dK=None, dV=None, work=None, a=None,
+                           negative_slope=0.2, B=None, scale=1.0, dB=None, dAr=None) -> int:
+        """the gradients of ``dropoutGat`` in TWO launches, for the same (p, seed, offset, head0).  Operands, outputs, ``work``,
+        ``a``, ``negative_slope``, ``B``, ``scale``, ``dB`` and ``dAr`` as ``gatBackward``.  With p = 0 every bit is that call's.
+        Anything else raises ValueError before the library is called."""
+        who = "dropoutGatBackward"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work, (("dAr", dAr, self._m, "k"),))
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others + (("a", a),))
+        ns = self._gat_args(who, Q, a, negative_slope)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work)
+        self._after_operands(who, Q, outs, (("B", B), ("a", a)), (("B", B), ("dB", dB), ("a", a)))
+        return self.dropout_gat_backward_ptr(heads, ns, a, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ,
+                                             ld["dQ"], dK, ld["dK"], dV, ld["dV"], work, dB, lddb, dAr, ld["dAr"], p, seed, offset, head0)
+
+    def dropout_gat_backward_ptr(self, heads: int, negative_slope: float, a, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int,
+                                 k: int, V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB,
+                                 lddb: int, dAr, lddar: int, p: float, seed: int, offset: int, head0: int) -> int:
+        """csr5hip_dropout_gat_backward on raw device pointers (or tensors); None for a, for B or for an output that is not wanted"""
+        return self._lib.csr5hip_dropout_gat_backward(self._h, int(heads), float(negative_slope), _ptr(a), float(scale), _ptr(B),
+                                                      int(ldb), _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                                      _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV),
+                                                      int(lddv), _ptr(work), _ptr(dB), int(lddb), _ptr(dAr), int(lddar), float(p),
+                                                      int(seed), int(offset), int(head0))
+
+    def dropoutMask(self, mask, p, seed, offset=0, head0=0) -> int:
+        """the mask of the dropped calls, for reference implementations and tests: ``mask`` is a 2-D ``torch.uint8`` GPU tensor
+        (nnz, H) with stride(1) == 1 (a column slice of a wider one is legal); element (e, h) becomes 1 where head ``head0 + h`` of
+        the entry of CSR rank e is KEPT, 0 where it is dropped.  It needs only the pattern's nnz: CSR and CSR5 format alike.  One
+        launch on the handle's stream.  Anything else raises ValueError before the library is called."""
+        who = "dropoutMask"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        if self._nnz is None:
+            raise ValueError(f"{who}: call inputCSR first")
+        if not hasattr(mask, "data_ptr") or not hasattr(mask, "stride"):
+            raise ValueError(f"{who}: mask must be a torch tensor")
+        if str(mask.dtype) != "torch.uint8":
+            raise ValueError(f"{who}: mask has dtype {mask.dtype}, it must be torch.uint8")
+        if mask.dim() != 2 or mask.shape[0] != self._nnz:
+            raise ValueError(f"{who}: mask must have shape ({self._nnz}, heads), not {tuple(mask.shape)}")
+        heads = int(mask.shape[1])
+        if mask.numel() and heads > 1 and mask.stride(1) != 1:
+            raise ValueError(f"{who}: mask must have stride(1) == 1, not {mask.stride()}")
+        if mask.numel() and mask.shape[0] > 1 and mask.stride(0) < heads:
+            raise ValueError(f"{who}: mask rows overlap (stride(0) {mask.stride(0)} < heads = {heads})")
+        if mask.device.type != "cuda":
+            raise ValueError(f"{who}: mask must live on the GPU, not {mask.device}")
+        ldm = max(int(mask.stride(0)), heads) if mask.shape[0] > 1 and heads else heads
+        return self.dropout_mask_ptr(heads, p, seed, offset, head0, mask, ldm)
+
+    def dropout_mask_ptr(self, heads: int, p: float, seed: int, offset: int, head0: int, mask, ldm: int) -> int:
+        """csr5hip_dropout_mask on a raw device pointer (or tensor): one byte per entry and head at mask[e * ldm + h]"""
+        return self._lib.csr5hip_dropout_mask(self._h, int(heads), float(p), int(seed), int(offset), int(head0), _ptr(mask), int(ldm))
+
     # -- softmax over the stored entries of every row (csr5hip.h csr5hip_row_softmax) -------------
     def _csr_value_args(self, who: str, named) -> None:
         """the checks of sddmm's ``out`` for every (name, tensor) of ``named``, whose last entry is the output: ValueError unless

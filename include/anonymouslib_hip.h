@@ -274,6 +274,53 @@ public:
                                          (void *)dK, lddk, (void *)dV, lddv, (void *)work, (void *)dB, lddb, (void *)dAr, lddar)
                   : _err;
     }
+    // extension: mhaEdgeBias / gat and their backwards with a seeded dropout mask on the attention weights (csr5hip_dropout.h: the
+    // mask's definition; p in [0, 1), seed and offset by value, head0 the absolute head of the operands' head 0), and the mask itself,
+    // one byte per entry and head at mask[e ldm + h]
+    int dropoutMha(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,
+                   const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d, ANONYMOUSLIB_VT *O, int ldo,
+                   double p, unsigned long long seed, unsigned long long offset = 0, int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_mha(_h, heads, scale, (const void *)B, ldb, (const void *)Q, ldq, (const void *)K, ldk, k,
+                                        (const void *)V, ldv, d, (void *)O, ldo, p, seed, offset, head0)
+                  : _err;
+    }
+    int dropoutMhaBackward(int heads, double scale, const ANONYMOUSLIB_VT *B, int ldb, const ANONYMOUSLIB_VT *Q, int ldq,
+                           const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,
+                           const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK, int lddk,
+                           ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work, ANONYMOUSLIB_VT *dB, int lddb, double p,
+                           unsigned long long seed, unsigned long long offset = 0, int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_mha_backward(_h, heads, scale, (const void *)B, ldb, (const void *)Q, ldq, (const void *)K, ldk, k,
+                                                 (const void *)V, ldv, d, (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk,
+                                                 (void *)dV, lddv, (void *)work, (void *)dB, lddb, p, seed, offset, head0)
+                  : _err;
+    }
+    int dropoutGat(int heads, double negative_slope, const ANONYMOUSLIB_VT *a, double scale, const ANONYMOUSLIB_VT *B, int ldb,
+                   const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V, int ldv, int d,
+                   ANONYMOUSLIB_VT *O, int ldo, double p, unsigned long long seed, unsigned long long offset = 0, int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_gat(_h, heads, negative_slope, (const void *)a, scale, (const void *)B, ldb, (const void *)Q, ldq,
+                                        (const void *)K, ldk, k, (const void *)V, ldv, d, (void *)O, ldo, p, seed, offset, head0)
+                  : _err;
+    }
+    int dropoutGatBackward(int heads, double negative_slope, const ANONYMOUSLIB_VT *a, double scale, const ANONYMOUSLIB_VT *B, int ldb,
+                           const ANONYMOUSLIB_VT *Q, int ldq, const ANONYMOUSLIB_VT *K, int ldk, int k, const ANONYMOUSLIB_VT *V,
+                           int ldv, int d, const ANONYMOUSLIB_VT *dO, int lddo, ANONYMOUSLIB_VT *dQ, int lddq, ANONYMOUSLIB_VT *dK,
+                           int lddk, ANONYMOUSLIB_VT *dV, int lddv, ANONYMOUSLIB_VT *work, ANONYMOUSLIB_VT *dB, int lddb,
+                           ANONYMOUSLIB_VT *dAr, int lddar, double p, unsigned long long seed, unsigned long long offset = 0,
+                           int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_gat_backward(_h, heads, negative_slope, (const void *)a, scale, (const void *)B, ldb,
+                                                 (const void *)Q, ldq, (const void *)K, ldk, k, (const void *)V, ldv, d,
+                                                 (const void *)dO, lddo, (void *)dQ, lddq, (void *)dK, lddk, (void *)dV, lddv,
+                                                 (void *)work, (void *)dB, lddb, (void *)dAr, lddar, p, seed, offset, head0)
+                  : _err;
+    }
+    int dropoutMask(int heads, double p, unsigned long long seed, unsigned long long offset, int head0, unsigned char *mask, int ldm)
+    {
+        return _h ? csr5hip_dropout_mask(_h, heads, p, seed, offset, head0, (void *)mask, ldm) : _err;
+    }
     // extension: softmax over the stored entries of every row and its gradient, nnz values in CSR order in and out (the order sddmm
     // writes and updateValues takes); device pointers; CSR and CSR5 format alike (csr5hip_row_softmax / csr5hip_row_softmax_grad)
     int rowSoftmax(const ANONYMOUSLIB_VT *scores, ANONYMOUSLIB_VT *out)

@@ -463,6 +463,10 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads,
  * fma(sum_c a_c LeakyReLU(q_c + k_c), scale, B) no choice of Q, K and B turns into a dot product -- are declared, with their contracts,
  * in csr5hip_gat.h, which this header includes at its end for the same reason; their declarations and exports are compared by
  * tests/test_gat_host.py. */
+/* Extension (not in the reference): csr5hip_dropout_mha, csr5hip_dropout_gat, their backwards and csr5hip_dropout_mask -- the edge-bias
+ * and the additive call with a seeded dropout mask on the attention weights, recomputed in the backward, and the mask itself -- are
+ * declared, with their contracts and the mask's definition, in csr5hip_dropout.h, which this header includes at its end for the same
+ * reason; their declarations and exports are compared by tests/test_attention_dropout_host.py. */
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -646,6 +650,7 @@ int csr5hip_multi_destroy(csr5hip_multi mh);
 #include "csr5hip_edge_bias.h"
 #include "csr5hip_lowp.h"
 #include "csr5hip_gat.h"
+#include "csr5hip_dropout.h"
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 """Resource table of the SpMV kernels from hipcc's own -Rpass-analysis=kernel-resource-usage remarks.
 
     python scripts/kernel_resources.py [--filter k_spmv] [--sigmas few|all] [--units 'attention_(bwd_)?edge'] > profiles/rNN_resources.md
-Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_attention_edge.hip, csr5_attention_bwd_edge.hip, csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip, csr5_attention_gat.hip, csr5_attention_bwd_gat.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
+Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_attention_edge.hip, csr5_attention_bwd_edge.hip, csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip, csr5_attention_gat.hip, csr5_attention_bwd_gat.hip, csr5_attention_drop.hip, csr5_attention_drop_gat.hip, csr5_attention_bwd_drop.hip, csr5_attention_bwd_drop_gat.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
 VGPRs / SGPRs / scratch / LDS / occupancy in waves per SIMD.  --units compiles only the translation units whose file name matches.
 Runs without a GPU."""
 import argparse
@@ -22,7 +22,7 @@ def demangle(names):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--filter", default="k_spmv|k_spmm|k_sddmm|k_row_softmax|k_attention|k_slab|k_calibrate|k_range|k_x_permute|k_refresh|k_companion")
+    ap.add_argument("--filter", default="k_spmv|k_spmm|k_sddmm|k_row_softmax|k_attention|k_dropout|k_slab|k_calibrate|k_range|k_x_permute|k_refresh|k_companion")
     ap.add_argument("--sigmas", default="few")
     ap.add_argument("--match", default=None, help="regex on the demangled name")
     ap.add_argument("--units", default=None, help="regex on the source file name: compile only these translation units")
@@ -46,6 +46,13 @@ def main():
                       ("csr5_attention_gat.hip", ["-DCSR5_ATTENTION_ONLY_F64"]), ("csr5_attention_gat.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
                       ("csr5_attention_bwd_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
                       ("csr5_attention_bwd_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
+                      ("csr5_attention_drop.hip", ["-DCSR5_ATTENTION_ONLY_F64"]), ("csr5_attention_drop.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
+                      ("csr5_attention_drop_gat.hip", ["-DCSR5_ATTENTION_ONLY_F64"]),
+                      ("csr5_attention_drop_gat.hip", ["-DCSR5_ATTENTION_ONLY_F32"]),
+                      ("csr5_attention_bwd_drop.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
+                      ("csr5_attention_bwd_drop.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
+                      ("csr5_attention_bwd_drop_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
+                      ("csr5_attention_bwd_drop_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
                       ("csr5_slab.hip", []), ("csr5_hot.hip", []),
                       ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F64"]), ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F32"]),
                       ("csr5_companion.hip", [])):
