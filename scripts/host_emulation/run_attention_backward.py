@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """csr5_attention_bwd.hip on the CPU, without a GPU: the kernel source is compiled for the host against the stand-in for the HIP
-runtime (fake/hip/hip_runtime.h) with -fsanitize=address,undefined, and run as a stand-alone program on matrices of tests/zoo.py
-and their transposes, both converted by the oracle (the transpose plays the transposed companion).
+runtime (fake/hip/hip_runtime.h) with -fsanitize=address,undefined, and run as a stand-alone program (attention_driver.cpp with
+that one unit; emulation.py) on matrices of tests/zoo.py and their transposes, both converted by the oracle (the transpose plays
+the transposed companion).
 
     python scripts/host_emulation/run_attention_backward.py [--matrices kat0,duplicates,...] [--kd 3x5,8x16] [--cxx clang++]
 
@@ -11,92 +12,24 @@ NAME^T for the transpose of any matrix.
 Per matrix, precision and (k, d): dQ, dK and dV against a float64 numpy reference (1e3 unit roundoffs of the gradient expression on
 absolute values: a check of the indexing, not the accuracy test), rows and columns without entries exactly +0, nothing written
 beyond column k or d, dQ alone without a workspace, and equal bits for sigma = 4, sigma = 7 with padded leading dimensions
-(element loads) and sigma = 16 (16-byte loads); the companion is converted at another sigma than the parent.  This exercises the
-indexing, the row classes and the arithmetic of the source; it says nothing about the gfx950 build."""
-import argparse
+(element loads, NaN in the padding) and sigma = 16 (16-byte loads); the companion is converted at another sigma than the parent.
+This exercises the indexing, the row classes and the arithmetic of the source; it says nothing about the gfx950 build."""
 import os
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from benchmark_spmv_using_csr5_amd import matrices as M  # noqa: E402
 from oracle.csr5_oracle import Oracle  # noqa: E402
-from tests import attention_edges as E  # noqa: E402
-from tests import sddmm_reference as S  # noqa: E402
-from tests import zoo  # noqa: E402
+from scripts.host_emulation import emulation as EMU  # noqa: E402
 
 KD = ((1, 1), (3, 5), (8, 16), (70, 40), (0, 7), (7, 0), (5, 300), (300, 5))
 DEFAULT = "kat0,duplicates,aligned64,aligned1024,one-row,aligned64^T,aligned1024^T,one-row^T"
-
-
-def transpose(mat):
-    """A^T in CSR with every column's entries in A's CSR order (a stable sort by column)"""
-    rows = np.repeat(np.arange(mat.m, dtype=np.int64), np.diff(mat.row_ptr))
-    cols = mat.col[:mat.nnz].astype(np.int64)
-    order = np.argsort(cols, kind="stable")
-    rp = np.zeros(mat.n + 1, dtype=np.int32)
-    rp[1:] = np.cumsum(np.bincount(cols, minlength=mat.n))
-    return M.CsrMatrix(mat.n, mat.m, rp, rows[order].astype(np.int32), np.ones(mat.nnz), mat.name + "^T")
-
-
-def matrices():
-    """name -> matrix: tests/zoo.py's, the duplicates matrix, class-edges and dealt; NAME^T is the transpose"""
-    mats = {m.name: m for m in zoo.small_zoo()}
-    mats["duplicates"] = S.duplicates_matrix()
-    mats["class-edges"] = E.class_edges()
-    mats["dealt"] = E.dealt()
-    return lambda name: transpose(mats[name[:-2]]) if name.endswith("^T") else mats[name]
-
-
-def build(cxx, out):
-    cmd = [cxx, "-std=c++20", "-x", "c++", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-Wno-unknown-pragmas", f"-I{HERE}/fake", f"-I{ROOT}/benchmark_spmv_using_csr5_amd/csrc", f"-I{ROOT}/include",
-           os.path.join(HERE, "attention_bwd_main.cpp"), "-o", out]
-    subprocess.check_call(cmd)
-
-
-def run(exe, tmp, orc, mat, matT, sigma, sigma_t, dtype, Q, K, V, dO, pad, want=7):
-    k, d = Q.shape[1], V.shape[1]
-    lds = (k + 3, k + 1, d + 2, d + 3, k + 1, k + 2, d + 1) if pad else (k, k, d, d, k, k, d)
-    fmt = orc.convert(64, sigma, mat.m, mat.row_ptr, mat.col, np.ones(mat.nnz))
-    fmt_t = orc.convert(64, sigma_t, matT.m, matT.row_ptr, matT.col, np.ones(matT.nnz))
-
-    def wide(t, ld):
-        w = np.full((t.shape[0], ld), 7.5, dtype=dtype)
-        w[:, :t.shape[1]] = t
-        return w
-    case, out = os.path.join(tmp, "case.bin"), os.path.join(tmp, "out.bin")
-    with open(case, "wb") as f:
-        np.array([mat.m, mat.n, mat.nnz, sigma, fmt.p, sigma_t, fmt_t.p, k, d, *lds, int(dtype == np.float64), want],
-                 dtype=np.int32).tofile(f)
-        for m_, f_ in ((mat, fmt), (matT, fmt_t)):
-            m_.row_ptr.astype(np.int32).tofile(f)
-            f_.col[:m_.nnz].astype(np.int32).tofile(f)
-            f_.tile_ptr.astype(np.uint32).tofile(f)
-        for t, ld in zip((Q, K, V, dO), lds[:4]):
-            wide(t, ld).tofile(f)
-    r = subprocess.run([exe, case, out], capture_output=True, text=True)
-    if r.returncode:
-        raise SystemExit(f"{mat.name} sigma {sigma}: exit {r.returncode}\n{r.stderr[-4000:]}")
-    flat = np.fromfile(out, dtype=dtype)
-    res, at = [], 0
-    for bit, rows, ld, width in ((1, mat.m, lds[4], k), (2, mat.n, lds[5], k), (4, mat.n, lds[6], d)):
-        g = flat[at:at + rows * ld].reshape(rows, ld)
-        at += rows * ld
-        assert np.isnan(g[:, width:]).all(), "written beyond the last column"
-        if want & bit:
-            res.append(np.ascontiguousarray(g[:, :width]))
-        else:
-            assert np.isnan(g).all(), "an output that was not wanted is written"
-            res.append(None)
-    return res
+NAMES = ("dQ", "dK", "dV")
 
 
 def reference(mat, Q, K, V, dO):
@@ -124,43 +57,29 @@ def reference(mat, Q, K, V, dO):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--matrices", default=DEFAULT)
-    ap.add_argument("--kd", default=",".join(f"{k}x{d}" for k, d in KD))
-    ap.add_argument("--cxx", default="/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else "clang++")
-    args = ap.parse_args()
-    kds = [tuple(int(v) for v in kd.split("x")) for kd in args.kd.split(",")]
+    args = EMU.arguments(DEFAULT, kd=KD, kinds=None)
     orc = Oracle()
-    mats = matrices()
+    mats = EMU.matrices()
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "attention_bwd_host")
-        build(args.cxx, exe)
-        for name in args.matrices.split(","):
-            mat = mats(name)
-            matT = transpose(mat)
-            empty = (np.diff(mat.row_ptr) == 0, np.diff(matT.row_ptr) == 0, np.diff(matT.row_ptr) == 0)
+        EMU.build(args.cxx, exe, ("attention_bwd",))
+        for name in args.matrices:
+            pat = EMU.Patterns(orc, mats(name))
             for dtype in (np.float64, np.float32):
                 u = float(np.finfo(dtype).eps) / 2
-                for k, d in kds:
-                    rng = np.random.default_rng(5)
-                    Q = (rng.uniform(-1, 1, (mat.m, k)) * 2).astype(dtype)
-                    K = rng.uniform(-1, 1, (mat.n, k)).astype(dtype)
-                    V = rng.uniform(-1, 1, (mat.n, d)).astype(dtype)
-                    dO = rng.uniform(-1, 1, (mat.m, d)).astype(dtype)
-                    ref, mag = reference(mat, Q, K, V, dO)
-                    first, worst = None, 0.0
-                    for sigma, sigma_t, pad in ((4, 16, False), (7, 4, True), (16, 7, False)):
-                        got = run(exe, tmp, orc, mat, matT, sigma, sigma_t, dtype, Q, K, V, dO, pad)
-                        for g, r, a, e, what in zip(got, ref, mag, empty, ("dQ", "dK", "dV")):
-                            err = np.abs(g - r)
-                            assert (err <= 1e3 * u * np.maximum(a, 1e-30) + 1e-300).all(), (name, dtype, k, d, sigma, what, float(err.max()))
-                            worst = max(worst, float(err.max()) if err.size else 0.0)
-                            assert not np.ascontiguousarray(g[e]).view(np.uint8).any(), f"{what}: a row without entries is not +0"
-                        first = got if first is None else first
-                        for g, g0, what in zip(got, first, ("dQ", "dK", "dV")):
-                            assert np.array_equal(g0.view(np.uint8), g.view(np.uint8)), (name, k, d, sigma, what, "bits")
-                    alone = run(exe, tmp, orc, mat, matT, 7, 4, dtype, Q, K, V, dO, True, want=1)  # no workspace, no companion
-                    assert np.array_equal(alone[0].view(np.uint8), first[0].view(np.uint8)), (name, k, d, "dQ alone")
+                for k, d in args.kd:
+                    ops = EMU.operands(pat.mat, 1, k, d, dtype)
+                    ref, mag = reference(pat.mat, *(t[:, 0] for t in ops))
+                    where = (name, np.dtype(dtype).name, k, d)
+
+                    def backward(sigma, sigma_t, pad, groups, want=7):
+                        return EMU.launch(exe, tmp, EMU.PLAIN, EMU.BACKWARD, pat, (sigma, sigma_t), ops, pad, want=want)[0]
+
+                    def judge(i, g):
+                        err = np.abs(g[:, 0] - ref[i])
+                        return err <= 1e3 * u * np.maximum(mag[i], 1e-30) + 1e-300, float(err.max()) if err.size else 0.0
+                    first, worst = EMU.check_configs(backward, NAMES, (pat.empty_r, pat.empty_c, pat.empty_c), where, judge)
+                    EMU.check_same(backward(7, 4, True, 0, want=1), first, NAMES, where, "dQ alone")  # no workspace, no companion
                     print(f"{name} {np.dtype(dtype).name} k={k} d={d}: ok, worst |error| {worst:.2e}", flush=True)
 
 

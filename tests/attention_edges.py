@@ -1,7 +1,7 @@
 """Patterns and EXACT expectations for the attention kernels at the places where they decide things (numpy only, no GPU): the
 edges of the line classes, hub lines beyond workgroup 0, and line counts at which the head groups of the packed calls hold
 three heads or all of them.  Used by tests/test_gpu_attention_edges.py, tests/test_attention_edges_host.py and the host-emulation
-scripts (scripts/host_emulation/run_*.py).
+scripts (scripts/host_emulation/emulation.py for run_*.py).
 
 THE CLASSES (csr5_attention_dev.h): a line of at most AT_G = 16 entries is taken by 16 lanes, one of 17 .. AT_WAVE_ROW = 512 by a
 wavefront, a longer one ("hub") by the workgroup after a barrier; up to AT_STAGE = 2 048 entries a hub is staged once, beyond

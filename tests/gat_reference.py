@@ -122,7 +122,7 @@ def numpy_reference(mat, a, ns, scale, bias, Q, K, V, dO, wrong=None):
 
 def within(g, r, a, smag, u):
     """elementwise: |g - r| <= 1e3 unit roundoffs of the expression on absolute values, times one plus the largest score magnitude
-    (NaN is outside): the host emulation's check of the indexing, scripts/host_emulation/run_mha_edge_bias.py's"""
+    (NaN is outside): the host emulation's check of the indexing, scripts/host_emulation/emulation.py's"""
     return np.abs(g - r) <= 1e3 * u * (1 + smag) * np.maximum(a, 1e-30) + 1e-300
 
 

@@ -102,7 +102,8 @@ def test_the_reference_rejects_two_wrong_kernels(dtype):
     """on the inputs of the host emulation (three heads, k = 3): what two wrong kernels would compute, judged by the emulation's own
     bound.  g from the sign of l a instead of u's: wherever a is negative the derivative is the other branch's, in dQ and dK (O, dV,
     dB and dAr do not see g).  The a of head 0 for every head: everything misses."""
-    from scripts.host_emulation import run_gat as EMU
+    from scripts.host_emulation import emulation as EMU
+    from scripts.host_emulation import run_gat
     for mat in _small():
         heads, k, d = 3, 3, 5
         a = EMU.distinct_a(heads, k, dtype)
@@ -110,7 +111,7 @@ def test_the_reference_rejects_two_wrong_kernels(dtype):
         bias = EMU.distinct_bias(mat.nnz, heads).astype(dtype)
         Q, K, V, dO = EMU.operands(mat, heads, k, d, dtype)
         u = float(np.finfo(dtype).eps) / 2
-        ns, c = float(dtype(EMU.SLOPE)), float(dtype(EMU.SCALE))
+        ns, c = float(dtype(run_gat.SLOPE)), float(dtype(EMU.SCALE))
         ref, mag, smag = G.numpy_reference(mat, a, ns, c, bias, Q, K, V, dO)
         for r, al in zip(ref, mag):  # the reference passes its own bound when rounded to the type: the bound is not empty
             assert G.within(r.astype(dtype).astype(np.float64), r, al, smag, u).all()

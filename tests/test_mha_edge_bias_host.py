@@ -15,7 +15,7 @@ import pytest
 
 from benchmark_spmv_using_csr5_amd import _capi
 from benchmark_spmv_using_csr5_amd import handle as H
-from scripts.host_emulation import run_mha_edge_bias as EMU
+from scripts.host_emulation import emulation as EMU
 from tests import attention_edges as E
 from tests import edge_bias_reference as EB
 from tests import sddmm_reference as S
@@ -249,7 +249,7 @@ def test_the_emulations_expectations_reject_wrong_kernels(name, dtype):
     a test that a wrong kernel would pass shows nothing."""
     mat, bias, (Q, K, V, dO) = _emulation_case(name, dtype)
     u = float(np.finfo(dtype).eps) / 2
-    ref, mag, smag = EMU.reference(mat, bias, Q, K, V, dO)
+    ref, mag, smag = EMU.edge_reference(mat, bias, Q, K, V, dO)
     # the reference passes its own bound when rounded to the type: the bound is not empty
     for r, a in zip(ref, mag):
         assert EMU.within(r.astype(dtype).astype(np.float64), r, a, smag, u).all()
@@ -258,22 +258,22 @@ def test_the_emulations_expectations_reject_wrong_kernels(name, dtype):
     assert not np.array_equal(amap, np.arange(mat.nnz))
 
     def misses(wrong, which):
-        return [what for g, r, a, what in zip(wrong, ref, mag, EMU.NAMES) if what in which and not EMU.within(g, r, a, smag, u).all()]
+        return [what for g, r, a, what in zip(wrong, ref, mag, EMU.EDGE_NAMES) if what in which and not EMU.within(g, r, a, smag, u).all()]
     # 1. the bias of head 0 used for every head
     head0 = np.repeat(bias[:, :1], bias.shape[1], axis=1)
-    assert misses(EMU.reference(mat, head0, Q, K, V, dO)[0], EMU.NAMES) == list(EMU.NAMES)
+    assert misses(EMU.edge_reference(mat, head0, Q, K, V, dO)[0], EMU.EDGE_NAMES) == list(EMU.EDGE_NAMES)
     # 2. the column kernel reads B at the A^T-CSR position q instead of at map[q]: the entry of rank e = map[q] gets B[q]
     at_position = np.empty_like(bias)
     at_position[amap] = bias
-    assert misses(EMU.reference(mat, bias, Q, K, V, dO, B_col=at_position)[0], ("dK", "dV")) == ["dK", "dV"]
+    assert misses(EMU.edge_reference(mat, bias, Q, K, V, dO, B_col=at_position)[0], ("dK", "dV")) == ["dK", "dV"]
     # 3. ldb taken as heads: element (e, h) read at e heads + h of the block of nnz (heads + 2) values (finite padding here, so
     #    that the miss is one of the bound and not of a NaN)
     flat = EMU.wide_bias(bias, bias.shape[1] + 2, fill=7.5).reshape(-1)
     packed = flat[:bias.size].reshape(bias.shape)
-    assert misses(EMU.reference(mat, packed, Q, K, V, dO)[0], EMU.NAMES) == list(EMU.NAMES)
+    assert misses(EMU.edge_reference(mat, packed, Q, K, V, dO)[0], EMU.EDGE_NAMES) == list(EMU.EDGE_NAMES)
     # and the NaN padding the emulation really uses poisons what such a kernel writes
     poisoned = EMU.wide_bias(bias, bias.shape[1] + 2).reshape(-1)[:bias.size].reshape(bias.shape)
-    assert np.isnan(EMU.reference(mat, poisoned, Q, K, V, dO)[0][0]).any()
+    assert np.isnan(EMU.edge_reference(mat, poisoned, Q, K, V, dO)[0][0]).any()
 
 
 def test_the_first_order_condition_of_the_float64_comparison():

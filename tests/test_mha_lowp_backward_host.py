@@ -269,7 +269,7 @@ def test_the_expectation_tells_one_rounding_from_two():
     x = tie +- 2^-30 relative.  ``round_once`` (the script's model of the wrong kernel) goes to the side the exact value lies on, the
     expectation ``to_words(float32(x))`` to the even neighbour; away from ties both agree."""
     sys.path.insert(0, ROOT)
-    from scripts.host_emulation.run_mha_lowp_backward import round_once
+    from scripts.host_emulation.emulation import round_once
     for kind, bits in (("bf16", 8), ("f16", 11)):
         ulp = 2.0 ** (1 - bits)                                    # of the operand type in [1, 2)
         even, odd = 1.0 + 2 * ulp, 1.0 + 3 * ulp                   # neighbours; the tie between them is 1 + 2.5 ulp
