@@ -252,6 +252,15 @@ SYMBOLS_DROPOUT = [
     ("csr5hip_dropout_mask", C.c_int, [_H, C.c_int] + _DROP + [C.c_void_p, C.c_int]),
 ]
 
+# the dropped calls on operands stored in 16 bits, bound by load() like the others: csr5hip_mha_lowp's and csr5hip_mha_lowp_backward's
+# arguments, each followed by p, seed, offset and head0.  A list of their own: tests/test_attention_dropout_host.py pins SYMBOLS_DROPOUT
+# and the lowp tests theirs; the declarations are in include/csr5hip_dropout_lowp.h, and tests/test_dropout_lowp_host.py compares them
+# with the exports.
+SYMBOLS_DROPOUT_LOWP = [
+    ("csr5hip_dropout_mha_lowp", C.c_int, SYMBOLS_LOWP[0][2] + _DROP),
+    ("csr5hip_dropout_mha_lowp_backward", C.c_int, SYMBOLS_LOWP_BACKWARD[0][2] + _DROP),
+]
+
 _lib = None
 
 
@@ -274,7 +283,8 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT + SYMBOLS_DROPOUT:
+    for name, restype, argtypes in (SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT + SYMBOLS_DROPOUT
+                                    + SYMBOLS_DROPOUT_LOWP):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -42,6 +42,8 @@ bias stays the caller's tensor, the handle is given no values and nothing about 
 Q, K, V (and such a 2-D bias) the forward is one ``A.mhaLowp`` -- 16-bit operands, fp32 arithmetic, whatever the handle's dtype --
 and the backward on an fp32 handle is one ``A.mhaLowpBackward`` on the kept 16-bit tensors (no widened copy, no cast); on an fp64
 handle it still widens what was kept and goes through ``A.mhaEdgeBiasBackward`` (a stopgap, see ``multihead_attention``).
+``dropout_attention`` with bf16 or fp16 tensors is one ``A.dropoutMhaLowp`` forward and one ``A.dropoutMhaLowpBackward`` backward on
+either handle dtype.
 
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
@@ -599,6 +601,39 @@ class _DropoutAttention(torch.autograd.Function):
         return (None,) + tuple(outs) + (None, dB, None, None, None)
 
 
+class _LowpDropoutAttention(torch.autograd.Function):
+    """bf16 / fp16 operands: the forward is ONE ``A.dropoutMhaLowp``, the backward ONE ``A.dropoutMhaLowpBackward`` on the kept
+    16-bit tensors and on dO as it arrives, with the same (p, seed, offset): 16-bit outputs for exactly the inputs that need a
+    gradient, a float32 workspace only when K or V needs one, dB the bias gradient itself.  On fp32 and fp64 handles alike: the
+    handle's values are not read, and this route has no earlier bit pattern to keep."""
+
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias, p, seed, offset):
+        Qc, Kc, Vc = (_packed(t.detach()) for t in (Q, K, V))
+        Bc = _rows_packed(bias.detach()) if bias is not None else None
+        _on_current_stream(A, Qc.device)
+        O = torch.empty((A._m,) + tuple(Vc.shape[1:]), dtype=Vc.dtype, device=Vc.device)  # (the kernel writes every row and head)
+        _check(A.dropoutMhaLowp(Qc, Kc, Vc, O, p, seed, offset, B=Bc, scale=scale), "dropoutMhaLowp")
+        ctx.A, ctx.scale, ctx.drop = A, scale, (p, seed, offset)
+        ctx.save_for_backward(Qc, Kc, Vc, Bc)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, B = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        need_bias = B is not None and ctx.needs_input_grad[5]
+        if not (any(need) or need_bias):
+            return (None,) * 9
+        A = ctx.A
+        dO, outs, work = _backward_plumbing(A, (Q, K, V), need, dO, Q.shape[1], torch.float32)
+        dB = torch.empty(tuple(B.shape), dtype=B.dtype, device=dO.device) if need_bias else None  # (every element is written)
+        p, seed, offset = ctx.drop
+        _check(A.dropoutMhaLowpBackward(Q, K, V, dO, p, seed, offset, dQ=outs[0], dK=outs[1], dV=outs[2], work=work, B=B,
+                                        scale=ctx.scale, dB=dB), "dropoutMhaLowpBackward")
+        return (None,) + tuple(outs) + (None, dB, None, None, None)  # (dB IS the gradient of the bias: no reduction, no cast)
+
+
 def dropout_attention(A, Q, K, V, p, seed, offset=0, scale=None, bias=None, training=True):
     """``multihead_attention`` with DROPOUT ON THE ATTENTION WEIGHTS inside the fused kernels: packed Q (m, H, k), K (n, H, k),
     V (n, H, d) -> (m, H, d), the weights ``softmax(scale * Q K^T + bias[:, h])`` over the stored entries of row i, each dropped
@@ -618,14 +653,31 @@ def dropout_attention(A, Q, K, V, p, seed, offset=0, scale=None, bias=None, trai
     ONE ``A.dropoutMha`` (one launch) and backward ONE ``A.dropoutMhaBackward`` (two launches) with the same (p, seed, offset), which
     recompute the mask: nothing of length nnz is kept or written beside ``grad_bias`` when the bias needs one.  Buffers, the
     companion and the workspace as ``multihead_attention``'s edge-bias route; the handle is given no values.  Nothing runs in
-    backward when nothing needs a gradient.  fp32 and fp64 handles; there is no 16-bit route."""
+    backward when nothing needs a gradient.  fp32 and fp64 handles.
+
+    A ``torch.bfloat16`` or ``torch.float16`` Q takes the 16-BIT ROUTE, whatever the handle's dtype: K, V and ``bias`` (``None`` or
+    2-D (nnz, H)) have Q's dtype -- ValueError otherwise --, forward is ONE ``A.dropoutMhaLowp`` and backward ONE
+    ``A.dropoutMhaLowpBackward`` (two launches) on the kept 16-bit tensors and on the incoming gradient as it arrives: fp32
+    arithmetic, every output rounded once, 16-bit ``torch.empty`` outputs for exactly the inputs that need a gradient, a float32
+    workspace of 4 m H values and the transposed companion only when K or V needs one, ``grad_bias`` the dB the kernel writes; no
+    widened copy and no cast, on fp32 and fp64 handles alike.  The mask is the one ``A.dropoutMask`` gives for the same
+    (p, seed, offset).  ``training=False`` and ``p == 0`` route as above: to ``multihead_attention``'s 16-bit route, or, with a
+    scale and no bias, to this one with p = 0, whose words are ``A.mhaLowp(B=None)``'s."""
     if bias is not None and not (hasattr(bias, "dim") and bias.dim() == 2):
         raise ValueError("dropout_attention: bias is None or a 2-D (nnz, H) tensor in CSR order")
     p, seed, offset = _dropout_numbers("dropout_attention", p, seed, offset)
+    lowp = getattr(Q, "dtype", None) in (torch.bfloat16, torch.float16)
+    if lowp:
+        for name, t in (("K", K), ("V", V), ("bias", bias)):
+            if t is not None and getattr(t, "dtype", None) != Q.dtype:
+                raise ValueError(f"dropout_attention: with bf16 / fp16 operands K, V and the bias (None or a 2-D (nnz, H) tensor) "
+                                 f"have Q's dtype {Q.dtype}; {name} has {getattr(t, 'dtype', type(t).__name__)}")
     if (not training or p == 0.0) and (bias is not None or scale is None):
         return multihead_attention(A, Q, K, V, scale=scale, bias=bias)
     if not training:
         p = 0.0  # (a scale without a bias: multihead_attention would read the handle's values as the bias; p = 0 drops nothing)
+    if lowp:
+        return _LowpDropoutAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias, p, seed, offset)
     return _DropoutAttention.apply(A, Q, K, V, 1.0 if scale is None else float(scale), bias, p, seed, offset)
 
 

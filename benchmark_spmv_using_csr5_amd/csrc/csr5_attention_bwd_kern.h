@@ -8,7 +8,8 @@
 // att_stored are no operation, and the kernels of the other units are, instruction for instruction, what they were without them
 // (scripts/compare_attention_asm.py).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED), as in csr5_attention_kern.h: the plain instantiations
-// carry no argument, no branch and no load for it.  Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
+// carry no argument, no branch and no load for it.  csr5_attention_bwd_drop_lowp.hip: the 16-bit backward under the dropout mask
+// (csr5hip_dropout_mha_lowp_backward; AttBwdLowpDropArgs, k_attention_bwd_lowp_drop).  Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
 #pragma once
 
 #include "csr5_attention_dev.h"
@@ -118,6 +119,15 @@ struct AttBwdDropGatArgs : AttBwdGatArgs<VT> {
     AttDrop<VT> drop;
 };
 
+// csr5hip_dropout_mha_lowp_backward (csr5_attention_bwd_drop_lowp.hip): AttBwdDropArgs<float>'s call on operands and outputs stored in
+// ST -- the 16-bit backward under the forward's mask, derived as AttBwdDropArgs is from the edge struct.  g, cd and the workspace are
+// float; the column kernel takes the entry's rank from the lowp bias struct's map
+template <typename ST_>
+struct AttBwdLowpDropArgs : AttBwdLowpArgs<ST_> {
+    static constexpr bool DROP = true;
+    AttDrop<float> drop;
+};
+
 // the arguments of head h alone: every operand moved to that head's slice, the workspace to that head's values of row 0 (biased:
 // the slopes and dS to that head's element, so that head 0 of the result is head h)
 template <typename ARGS>
@@ -202,6 +212,12 @@ __device__ __forceinline__ void bwd_store_ds(const ARGS &A, const int t0, const 
             A.dS[((size_t)t0 * A.T + (size_t)rem0 + (size_t)j) * A.ldds] = att_stored<typename ARGS::ST>(ds);
 }
 
+// whether the chains of an instantiation take a 32-byte block in two halves (att_score's HALVES): the dropped bf16 kernels only --
+// false, and att_score's code untouched, for every other argument struct.  (fp16 has no scratch without it and is 4 to 8 % faster
+// that way: DESIGN.md section 31)
+template <typename VT, typename ARGS>
+constexpr bool bwd_halves = ARGS::DROP && __is_same(typename ARGS::ST, __bf16);
+
 // the score of the entry (i, j) alone; av: its value (read only when biased)
 template <typename VT, bool VEC, typename ARGS>
 __device__ __forceinline__ VT bwd_score(const ARGS &A, const size_t i, const size_t j, const VT av)
@@ -209,7 +225,7 @@ __device__ __forceinline__ VT bwd_score(const ARGS &A, const size_t i, const siz
     if constexpr (ARGS::GAT) {
         return att_bias_score(A.bias, 0, att_gat_z<VT>(A.Q + i * A.ldq, A.K + j * A.ldk, A.gat.a, A.gat.ns, A.k), av);
     } else {
-        const VT s = att_score<VT, VEC>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
+        const VT s = att_score<VT, VEC, bwd_halves<VT, ARGS>>(A.Q + i * A.ldq, A.K + j * A.ldk, A.k);
         if constexpr (ARGS::BIASED)
             return att_bias_score(A.bias, 0, s, av);
         else
@@ -222,7 +238,7 @@ template <typename VT, bool VEC, typename ARGS>
 __device__ __forceinline__ void bwd_entry(const ARGS &A, const size_t i, const size_t j, const VT av, const VT g, VT &s, VT &dp)
 {
     s = bwd_score<VT, VEC>(A, i, j, av);
-    dp = att_score<VT, VEC>(A.dO + i * A.lddo, A.V + j * A.ldv, A.d);
+    dp = att_score<VT, VEC, bwd_halves<VT, ARGS>>(A.dO + i * A.lddo, A.V + j * A.ldv, A.d);
     if constexpr (ARGS::DROP)
         dp = g * dp;
 }
@@ -920,6 +936,16 @@ __global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_BWD_LOWP_WAVES k_attention_
     CSR5_ATTENTION_BWD_KERNEL_BODY(true)
 }
 
+// the dropped 16-bit call: k_attention_bwd_lowp on its derived argument struct, under the same 6-wave attribute.  Its chains take a
+// 32-byte block in halves where ST is bf16 (bwd_halves, att_score's HALVES): with the whole block widened next to the hash's live
+// words the bf16 kernels with 16-byte loads had 16 (row kernel) and 28 (column kernel) bytes of scratch per lane
+template <typename ST, bool VEC, bool COL>
+__global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_BWD_LOWP_WAVES k_attention_bwd_lowp_drop(const AttBwdLowpDropArgs<ST> A)
+{
+    using VT = float;
+    CSR5_ATTENTION_BWD_KERNEL_BODY(true)
+}
+
 // the kernels of an argument struct, as overloads (csr5_attention_kern.h attention_enqueue).  COL: the column kernel
 template <bool VEC, bool COL, bool MH, typename VT>
 static void attention_bwd_enqueue(const AttBwdArgs<VT> &A, const dim3 grid, hipStream_t s)
@@ -956,6 +982,11 @@ template <bool VEC, bool COL, bool MH, typename ST>
 static void attention_bwd_enqueue(const AttBwdLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_bwd_lowp<ST, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool COL, bool MH, typename ST>
+static void attention_bwd_enqueue(const AttBwdLowpDropArgs<ST> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_bwd_lowp_drop<ST, VEC, COL>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 
 // the pattern walked and the head groups of one side's launch.  groups: the head groups over grid.y, 0 for the rule

@@ -77,13 +77,32 @@ __device__ __forceinline__ void att_load16(const ST *__restrict__ p, VT *o)
 // the chain of the definition over one row of Q and one of K.  VEC: blocks of 32 bytes by 16-byte loads, the rest by elements.
 // ST: the type the rows are stored in, VT unless the caller's pointers say otherwise (csr5_attention_lowp.hip: bf16 / fp16 rows, the
 // chain in float); every element is widened by a cast, which is exact, and the chain runs c = 0, 1, 2, ... whatever the load width.
-template <typename VT, bool VEC, typename ST>
+// HALVES (csr5_attention_bwd_drop_lowp.hip's bf16 kernels only): a 32-byte block is widened and consumed 16 bytes at a time, the
+// accumulator pinned in a register between the halves, so that at most 8 + 8 widened elements are live next to the mask's hash
+// instead of 16 + 16 -- the same FMAs in the same order, the same bits; without it those kernels spill under their 6-wave attribute
+// 
+template <typename VT, bool VEC, bool HALVES = false, typename ST>
 __device__ __forceinline__ VT att_score(const ST *__restrict__ q, const ST *__restrict__ kr, const int k)
 {
     constexpr int PER = 16 / (int)sizeof(ST);
     VT acc = (VT)0;
     int c = 0;
-    if constexpr (VEC) {
+    if constexpr (VEC && HALVES) {
+        for (; c + 2 * PER <= k; c += 2 * PER) {
+#pragma unroll
+            for (int half = 0; half < 2; half++) {
+                VT a[PER], b[PER];
+                att_load16<ST>(q + c + half * PER, a);
+                att_load16<ST>(kr + c + half * PER, b);
+#pragma unroll
+                for (int j = 0; j < PER; j++)
+                    acc = fma_vt(a[j], b[j], acc);
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("" : "+v"(acc));
+#endif
+            }
+        }
+    } else if constexpr (VEC) {
         for (; c + 2 * PER <= k; c += 2 * PER) {
             VT a[2 * PER], b[2 * PER];
             att_load16<ST>(q + c, a);

@@ -9,6 +9,7 @@
 // were without them (scripts/compare_attention_asm.py).
 // THE BIAS IS A COMPILE-TIME PROPERTY OF THE ARGUMENT STRUCT (ARGS::BIASED): the plain instantiations carry no bias argument,
 // no branch and no load for it -- their kernarg block and their code are those of the templates without it.
+// csr5_attention_drop_lowp.hip: the 16-bit call with the dropout mask (csr5hip_dropout_mha_lowp; AttLowpDropArgs, k_attention_lowp_drop).
 // Include it after `#pragma clang fp contract(off)`; gfx950 (wave64) only.
 #pragma once
 
@@ -109,6 +110,14 @@ struct AttLowpArgs {
     ST *O;
     int ldq, ldk, ldv, ldo;
     AttEdgeBiasLowp<ST> bias;
+};
+
+// csr5hip_dropout_mha_lowp (csr5_attention_drop_lowp.hip): AttDropArgs<float>'s call on operands stored in ST -- the 16-bit call with
+// the dropout mask on the float weights, derived as AttDropArgs is from the edge struct.  cd is float, as everything computed
+template <typename ST_>
+struct AttLowpDropArgs : AttLowpArgs<ST_> {
+    static constexpr bool DROP = true;
+    AttDrop<float> drop;
 };
 
 // ---- rows of at most 16 entries (empty rows included): 16 lanes per row, 4 rows of the wavefront per pass ------------------
@@ -491,6 +500,14 @@ __global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_LOWP_WAVES k_attention_lowp
     CSR5_ATTENTION_KERNEL_BODY(true)
 }
 
+// the dropped 16-bit call: k_attention_lowp on its derived argument struct, under the same occupancy attribute
+template <typename ST, bool VEC>
+__global__ void __launch_bounds__(AT_BLOCK) CSR5_ATT_LOWP_WAVES k_attention_lowp_drop(const AttLowpDropArgs<ST> A)
+{
+    using VT = float;
+    CSR5_ATTENTION_KERNEL_BODY(true)
+}
+
 // the kernels of an argument struct, as overloads, so that the launcher below is written once.  MH: only the plain call has a
 // single-head instantiation; the others are always the packed call
 template <bool VEC, bool MH, typename VT>
@@ -527,6 +544,11 @@ template <bool VEC, bool MH, typename ST>
 static void attention_enqueue(const AttLowpArgs<ST> &A, const dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_attention_lowp<ST, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
+}
+template <bool VEC, bool MH, typename ST>
+static void attention_enqueue(const AttLowpDropArgs<ST> &A, const dim3 grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_attention_lowp_drop<ST, VEC>), grid, dim3(AT_BLOCK), 0, s, A);
 }
 
 // the pattern, the operands and the head groups of a launch.  VT: the type the operands are stored in

@@ -497,7 +497,7 @@ static bool att_drop_ok(const AttCall &c)
 }
 
 // ---- attention on the pattern (csr5_attention*.hip) ---------------------------------------------------------------------------
-// The twelve entry points, and the four dropped ones further down, fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
+// The twelve entry points, and the six dropped ones further down, fill a call descriptor (csr5_internal.h) and share ONE path per direction: the checks in ONE order, the
 // trivial cases, the launch.  The single-head calls are heads = 1.  The forward reads row_ptr, tile_ptr and the tile-ordered
 // column_index of the parent, whatever path spmv() takes (biased: its tile-ordered values too); it allocates nothing and changes
 // nothing: enqueue-only.  lowp: the call names the type its operands are stored in (operand_type, judged here); the others take the handle's.
@@ -523,7 +523,9 @@ static int attention_forward(csr5hip_handle h, AttVariant variant, bool lowp, in
         return CSR5HIP_UNKOWN_FORMAT;
     if (c.heads == 0 || c.d == 0 || h->g.m <= 0)
         return CSR5HIP_SUCCESS;
-    if (lowp)
+    if (lowp && variant == ATT_DROP)
+        HIP_TRY(launch_mha_lowp_drop(h->g, h->d, operand_type, c, h->stream));
+    else if (lowp)
         HIP_TRY(launch_mha_lowp(h->g, h->d, operand_type, c, h->stream));
     else if (variant == ATT_PLAIN)
         HIP_TRY(launch_mha(h->g, h->d, h->value_type, c, h->stream));
@@ -591,7 +593,9 @@ static int attention_backward(csr5hip_handle h, const char *name, AttVariant var
         c.dt = &h->comp.at->d;
         c.map = mapped ? (const uint32_t *)h->comp[A_MAP].ptr : nullptr;
     }
-    if (lowp)
+    if (lowp && variant == ATT_DROP)
+        HIP_TRY(launch_mha_lowp_drop_bwd(h->g, h->d, operand_type, c, h->stream));
+    else if (lowp)
         HIP_TRY(launch_mha_lowp_bwd(h->g, h->d, operand_type, c, h->stream));
     else if (variant == ATT_PLAIN)
         HIP_TRY(launch_mha_bwd(h->g, h->d, h->value_type, c, h->stream));
@@ -759,6 +763,29 @@ int csr5hip_dropout_mha_backward(csr5hip_handle h, int heads, double scale, cons
     c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
     att_set_dropout(c, p, seed, offset, head0);
     return attention_backward(h, "csr5hip_dropout_mha_backward", ATT_DROP, false, 0, c);
+}
+
+// the same two on operands stored in bf16 / fp16 (csr5hip_dropout_lowp.h): the pair (ATT_DROP, lowp) picks the 16-bit dropped kernels
+int csr5hip_dropout_mha_lowp(csr5hip_handle h, int operand_type, int heads, double scale, const void *d_B, int ldb, const void *d_Q,
+                             int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d, void *d_O, int ldo, double p,
+                             unsigned long long seed, unsigned long long offset, int head0)
+{
+    AttCall c = att_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_O, ldo);
+    c.scale = scale; c.B = d_B; c.ldb = ldb;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_forward(h, ATT_DROP, true, operand_type, c);
+}
+
+int csr5hip_dropout_mha_lowp_backward(csr5hip_handle h, int operand_type, int heads, double scale, const void *d_B, int ldb,
+                                      const void *d_Q, int ldq, const void *d_K, int ldk, int k, const void *d_V, int ldv, int d,
+                                      const void *d_dO, int lddo, void *d_dQ, int lddq, void *d_dK, int lddk, void *d_dV, int lddv,
+                                      void *d_work, void *d_dB, int lddb, double p, unsigned long long seed, unsigned long long offset,
+                                      int head0)
+{
+    AttBwdCall c = att_bwd_call(heads, d_Q, ldq, d_K, ldk, k, d_V, ldv, d, d_dO, lddo, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_work);
+    c.scale = scale; c.B = d_B; c.ldb = ldb; c.dS = d_dB; c.ldds = lddb;
+    att_set_dropout(c, p, seed, offset, head0);
+    return attention_backward(h, "csr5hip_dropout_mha_lowp_backward", ATT_DROP, true, operand_type, c);
 }
 
 int csr5hip_dropout_gat(csr5hip_handle h, int heads, double negative_slope, const void *d_a, double scale, const void *d_B, int ldb,

@@ -332,6 +332,10 @@ hipError_t launch_gat_drop(const Geometry &g, const DeviceArrays &d, int value_t
 hipError_t launch_mha_drop_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_gat_drop_bwd(const Geometry &g, const DeviceArrays &d, int value_type, const AttBwdCall &c, hipStream_t s);
 hipError_t launch_dropout_mask(int nnz, const AttCall &c, unsigned char *mask, int ldm, hipStream_t s);
+// csr5_attention_drop_lowp.hip, csr5_attention_bwd_drop_lowp.hip: launch_mha_drop and launch_mha_drop_bwd on operands stored in 16 bits,
+// by launch_mha_lowp's and launch_mha_lowp_bwd's conventions (operand_type checked by the caller; float arithmetic, cd and workspace)
+hipError_t launch_mha_lowp_drop(const Geometry &g, const DeviceArrays &d, int operand_type, const AttCall &c, hipStream_t s);
+hipError_t launch_mha_lowp_drop_bwd(const Geometry &g, const DeviceArrays &d, int operand_type, const AttBwdCall &c, hipStream_t s);
 // csr5_hot.hip: the slab child's SpMV when its column words are hot-encoded (persistent range kernel + finish)
 hipError_t launch_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, void *y,
                            const SpmvOptions &opt, hipStream_t s);

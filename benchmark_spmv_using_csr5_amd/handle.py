@@ -730,6 +730,64 @@ class anonymouslibHandle:
                                                       _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV), int(lddv), _ptr(work),
                                                       _ptr(dB), int(lddb), float(p), int(seed), int(offset), int(head0))
 
+    # -- the dropped dot-product calls with operands stored in bf16 / fp16, computed in fp32 (csr5hip_dropout_lowp.h) ------------
+    def dropoutMhaLowp(self, Q, K, V, O, p, seed, offset=0, head0=0, B=None, scale=1.0) -> int:
+        """``dropoutMha`` on operands STORED IN 16 BITS: Q, K, V, O and B (when given) are all ``torch.bfloat16`` or all
+        ``torch.float16``, WHATEVER THE HANDLE'S DTYPE.  Everything is computed in fp32 -- the kept weights' factor is
+        ``float(1 / (1 - p))`` -- and O is rounded once where it is stored, so the result is, bit for bit (NaN payloads apart),
+        ``dropoutMha`` on an fp32 handle for the widened operands, cast to the operand type.  The mask is ``dropoutMha``'s and
+        ``dropoutMask``'s for the same (p, seed, offset, head0); with p = 0 every word is ``mhaLowp``'s.  The mask's arguments are
+        judged first, as ``dropoutMha`` judges them; dtypes, layouts, strides, devices and aliasing as ``mhaLowp``.  ONE launch; the
+        handle is left untouched.  Anything else raises ValueError before the library is called."""
+        who = "dropoutMhaLowp"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ot, dt = self._lowp_type(who, Q)
+        ins, outs = self._forward_operands(Q, K, V, O)
+        scale, ldb, _ = self._mha_edge_args(who, self._mha_heads(Q), scale, B, None, (), dt)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, None, dt)
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B),))
+        return self.dropout_mha_lowp_ptr(ot, heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, O, ld["O"], p, seed, offset,
+                                         head0)
+
+    def dropout_mha_lowp_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int, V,
+                             ldv: int, d: int, O, ldo: int, p: float, seed: int, offset: int, head0: int) -> int:
+        """csr5hip_dropout_mha_lowp on raw device pointers (or tensors): operand_type ``_capi.BF16`` or ``_capi.F16``, the leading
+        dimensions in elements of that type; B None for no bias"""
+        return self._lib.csr5hip_dropout_mha_lowp(self._h, int(operand_type), int(heads), float(scale), _ptr(B), int(ldb), _ptr(Q),
+                                                  int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d), _ptr(O), int(ldo),
+                                                  float(p), int(seed), int(offset), int(head0))
+
+    def dropoutMhaLowpBackward(self, Q, K, V, dO, p, seed, offset=0, head0=0, dQ=None, dK=None, dV=None, work=None, B=None, scale=1.0,
+                               dB=None) -> int:
+        """the gradients of ``dropoutMhaLowp`` in TWO launches, for the same (p, seed, offset, head0): ``dropoutMhaBackward`` on
+        operands STORED IN 16 BITS.  Q, K, V, dO, B (when given) and the wanted outputs dQ, dK, dV, dB are all ``torch.bfloat16`` or
+        all ``torch.float16``, WHATEVER THE HANDLE'S DTYPE; ``work`` is a contiguous 1-D ``torch.float32`` tensor of at least
+        4 m H values.  Everything is computed in fp32 and each output is rounded once where it is stored: each is, bit for bit (NaN
+        payloads apart), what ``dropoutMhaBackward`` on an fp32 handle writes for the widened operands, cast to the operand type,
+        and with p = 0 every word is ``mhaLowpBackward``'s.  dK and dV need ``work`` and the transposed companion
+        (``buildTranspose``; it is never built here), dB and dQ neither.  Everything else as ``mhaLowpBackward``.  Anything else
+        raises ValueError before the library is called."""
+        who = "dropoutMhaLowpBackward"
+        p, seed, offset, head0 = self._dropout_args(who, p, seed, offset, head0)
+        ot, dt = self._lowp_type(who, Q)
+        ins, outs, others = self._backward_operands(Q, K, V, dO, dQ, dK, dV, work)
+        scale, ldb, lddb = self._mha_edge_args(who, self._mha_heads(Q), scale, B, dB, others, dt)
+        heads, k, d, ld = self._operand_args(who, 3, ins, outs, work, dt, "torch.float32")
+        self._after_operands(who, Q, outs, (("B", B),), (("B", B), ("dB", dB)))
+        return self.dropout_mha_lowp_backward_ptr(ot, heads, scale, B, ldb, Q, ld["Q"], K, ld["K"], k, V, ld["V"], d, dO, ld["dO"], dQ,
+                                                  ld["dQ"], dK, ld["dK"], dV, ld["dV"], work, dB, lddb, p, seed, offset, head0)
+
+    def dropout_mha_lowp_backward_ptr(self, operand_type: int, heads: int, scale: float, B, ldb: int, Q, ldq: int, K, ldk: int, k: int,
+                                      V, ldv: int, d: int, dO, lddo: int, dQ, lddq: int, dK, lddk: int, dV, lddv: int, work, dB,
+                                      lddb: int, p: float, seed: int, offset: int, head0: int) -> int:
+        """csr5hip_dropout_mha_lowp_backward on raw device pointers (or tensors): operand_type ``_capi.BF16`` or ``_capi.F16``, the
+        leading dimensions in elements of that type, work float; None for B or for an output that is not wanted"""
+        return self._lib.csr5hip_dropout_mha_lowp_backward(self._h, int(operand_type), int(heads), float(scale), _ptr(B), int(ldb),
+                                                           _ptr(Q), int(ldq), _ptr(K), int(ldk), int(k), _ptr(V), int(ldv), int(d),
+                                                           _ptr(dO), int(lddo), _ptr(dQ), int(lddq), _ptr(dK), int(lddk), _ptr(dV),
+                                                           int(lddv), _ptr(work), _ptr(dB), int(lddb), float(p), int(seed),
+                                                           int(offset), int(head0))
+
     def dropoutGat(self, Q, K, V, O, p, seed, offset=0, head0=0, a=None, negative_slope=0.2, B=None, scale=1.0) -> int:
         """``gat`` with ``dropoutMha``'s dropout on the attention weights, in ONE launch -- PyG's ``GATConv(dropout=p)`` recipe.  The
         score is ``gat``'s, bit for bit; the mask and everything after the score are ``dropoutMha``'s.  With p = 0 every bit is

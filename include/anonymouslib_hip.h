@@ -317,6 +317,26 @@ public:
                                                  (void *)work, (void *)dB, lddb, (void *)dAr, lddar, p, seed, offset, head0)
                   : _err;
     }
+    // extension: dropoutMha / dropoutMhaBackward on operands STORED in 16 bits -- operand_type, the void * operands, their leading
+    // dimensions and the FLOAT workspace as mhaLowp / mhaLowpBackward, the mask as dropoutMha; computed in fp32, every output rounded
+    // once (csr5hip_dropout_lowp.h)
+    int dropoutMhaLowp(int operand_type, int heads, double scale, const void *B, int ldb, const void *Q, int ldq, const void *K, int ldk,
+                       int k, const void *V, int ldv, int d, void *O, int ldo, double p, unsigned long long seed,
+                       unsigned long long offset = 0, int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_mha_lowp(_h, operand_type, heads, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, d, O, ldo, p, seed,
+                                             offset, head0)
+                  : _err;
+    }
+    int dropoutMhaLowpBackward(int operand_type, int heads, double scale, const void *B, int ldb, const void *Q, int ldq, const void *K,
+                               int ldk, int k, const void *V, int ldv, int d, const void *dO, int lddo, void *dQ, int lddq, void *dK,
+                               int lddk, void *dV, int lddv, void *work, void *dB, int lddb, double p, unsigned long long seed,
+                               unsigned long long offset = 0, int head0 = 0)
+    {
+        return _h ? csr5hip_dropout_mha_lowp_backward(_h, operand_type, heads, scale, B, ldb, Q, ldq, K, ldk, k, V, ldv, d, dO, lddo, dQ,
+                                                      lddq, dK, lddk, dV, lddv, work, dB, lddb, p, seed, offset, head0)
+                  : _err;
+    }
     int dropoutMask(int heads, double p, unsigned long long seed, unsigned long long offset, int head0, unsigned char *mask, int ldm)
     {
         return _h ? csr5hip_dropout_mask(_h, heads, p, seed, offset, head0, (void *)mask, ldm) : _err;

@@ -467,6 +467,10 @@ int csr5hip_mha_backward(csr5hip_handle h, int heads,
  * and the additive call with a seeded dropout mask on the attention weights, recomputed in the backward, and the mask itself -- are
  * declared, with their contracts and the mask's definition, in csr5hip_dropout.h, which this header includes at its end for the same
  * reason; their declarations and exports are compared by tests/test_attention_dropout_host.py. */
+/* Extension (not in the reference): csr5hip_dropout_mha_lowp and csr5hip_dropout_mha_lowp_backward -- the dropped dot-product calls on
+ * operands stored in bf16 or fp16, computed in fp32 and rounded once -- are declared, with their contracts, in csr5hip_dropout_lowp.h,
+ * which this header includes at its end for the same reason; their declarations and exports are compared by
+ * tests/test_dropout_lowp_host.py. */
 /* `count` back-to-back spmv() calls replayed from one captured hipGraph (the reference CLI's timed
  * loop, CSR5_cuda/main.cu:96-99, without per-launch host cost). */
 int csr5hip_spmv_repeat(csr5hip_handle h, double alpha, void *d_y, int count);
@@ -651,6 +655,7 @@ int csr5hip_multi_destroy(csr5hip_multi mh);
 #include "csr5hip_lowp.h"
 #include "csr5hip_gat.h"
 #include "csr5hip_dropout.h"
+#include "csr5hip_dropout_lowp.h"
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 two biased units (csr5_attention_bias.hip, csr5_attention_bwd_bias.hip), the two edge-biased ones (csr5_attention_edge.hip,
 csr5_attention_bwd_edge.hip), the 16-bit ones (csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip) the additive-score ones
 (csr5_attention_gat.hip, csr5_attention_bwd_gat.hip) and the dropped ones (csr5_attention_drop.hip, csr5_attention_drop_gat.hip,
-csr5_attention_bwd_drop.hip, csr5_attention_bwd_drop_gat.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
+csr5_attention_bwd_drop.hip, csr5_attention_bwd_drop_gat.hip, csr5_attention_drop_lowp.hip, csr5_attention_bwd_drop_lowp.hip) for gfx950 to assembly (hipcc -O3 --cuda-device-only
 -S, once per value or operand type) from a git revision and from the working tree, and compares every kernel of the revision
 (k_attention<..>, k_attention_bwd<..>, k_attention_biased<..>, k_attention_bwd_biased<..>, k_attention_edge<..>, k_attention_bwd_edge<..>, k_attention_lowp<..>, k_attention_bwd_lowp<..>, k_attention_gat<..>, k_attention_bwd_gat<..>) with the kernel of the same symbol
 now, instruction for instruction and register for register.  No GPU needed.
@@ -38,7 +38,9 @@ UNITS = (("csr5_attention.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention.hip
          ("csr5_attention_drop.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_drop.hip", "CSR5_ATTENTION_ONLY_F32"),
          ("csr5_attention_drop_gat.hip", "CSR5_ATTENTION_ONLY_F64"), ("csr5_attention_drop_gat.hip", "CSR5_ATTENTION_ONLY_F32"),
          ("csr5_attention_bwd_drop.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_drop.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
-         ("csr5_attention_bwd_drop_gat.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_drop_gat.hip", "CSR5_ATTENTION_BWD_ONLY_F32"))
+         ("csr5_attention_bwd_drop_gat.hip", "CSR5_ATTENTION_BWD_ONLY_F64"), ("csr5_attention_bwd_drop_gat.hip", "CSR5_ATTENTION_BWD_ONLY_F32"),
+         ("csr5_attention_drop_lowp.hip", "CSR5_LOWP_ONLY_BF16"), ("csr5_attention_drop_lowp.hip", "CSR5_LOWP_ONLY_F16"),
+         ("csr5_attention_bwd_drop_lowp.hip", "CSR5_LOWP_ONLY_BF16"), ("csr5_attention_bwd_drop_lowp.hip", "CSR5_LOWP_ONLY_F16"))
 
 
 def kernels(tree, src, define, out):

@@ -97,10 +97,20 @@ namespace csr5 { ABSENT_FWD(launch_gat_drop, "ATTENTION_DROP_GAT") }
 #else
 namespace csr5 { ABSENT_BWD(launch_gat_drop_bwd, "ATTENTION_BWD_DROP_GAT") }
 #endif
+#ifdef EMU_ATTENTION_DROP_LOWP
+#include "csr5_attention_drop_lowp.hip"
+#else
+namespace csr5 { ABSENT_FWD(launch_mha_lowp_drop, "ATTENTION_DROP_LOWP") }
+#endif
+#ifdef EMU_ATTENTION_BWD_DROP_LOWP
+#include "csr5_attention_bwd_drop_lowp.hip"
+#else
+namespace csr5 { ABSENT_BWD(launch_mha_lowp_drop_bwd, "ATTENTION_BWD_DROP_LOWP") }
+#endif
 
 // The case file's header: emulation.py's MAGIC, the number of fields, then the fields IN THIS ORDER (emulation.py FIELDS).
 constexpr uint32_t MAGIC = 0x35545441; // "ATT5"
-enum Variant { PLAIN, BIASED, EDGE, LOWP, GAT, DROP, DROP_GAT, VARIANTS };
+enum Variant { PLAIN, BIASED, EDGE, LOWP, GAT, DROP, DROP_GAT, DROP_LOWP, VARIANTS };
 enum Mode { FORWARD, BACKWARD, MASK };
 struct Header {
     int32_t variant, mode, kind;            // kind: CSR5HIP_F64, CSR5HIP_F32, CSR5HIP_BF16, CSR5HIP_F16
@@ -196,9 +206,9 @@ static int launch(int variant, int mode, const Pattern &A, int type, const csr5:
     using Forward = hipError_t(const Geometry &, const DeviceArrays &, int, const AttCall &, hipStream_t);
     using Backward = hipError_t(const Geometry &, const DeviceArrays &, int, const AttBwdCall &, hipStream_t);
     static Forward *const forward[VARIANTS] = {launch_mha, launch_mha_biased, launch_mha_edge, launch_mha_lowp, launch_gat, launch_mha_drop,
-                                               launch_gat_drop};
+                                               launch_gat_drop, launch_mha_lowp_drop};
     static Backward *const backward[VARIANTS] = {launch_mha_bwd, launch_mha_biased_bwd, launch_mha_edge_bwd, launch_mha_lowp_bwd,
-                                                 launch_gat_bwd, launch_mha_drop_bwd, launch_gat_drop_bwd};
+                                                 launch_gat_bwd, launch_mha_drop_bwd, launch_gat_drop_bwd, launch_mha_lowp_drop_bwd};
     return mode == FORWARD ? forward[variant](A.g, A.da, type, c, nullptr) : backward[variant](A.g, A.da, type, c, nullptr);
 }
 
@@ -215,7 +225,7 @@ int main(int argc, char **argv)
     }
     if (fread(&h, sizeof h, 1, f) != 1 || fread(&x, sizeof x, 1, f) != 1) return 2;
     if (h.variant < 0 || h.variant >= VARIANTS || h.mode < FORWARD || h.mode > MASK || h.kind < CSR5HIP_F64 || h.kind > CSR5HIP_F16 ||
-        (h.variant == LOWP) != (h.kind >= CSR5HIP_BF16) || (h.mode == MASK && h.variant != DROP && h.variant != DROP_GAT))
+        (h.variant == LOWP || h.variant == DROP_LOWP) != (h.kind >= CSR5HIP_BF16) || (h.mode == MASK && h.variant != DROP && h.variant != DROP_GAT))
         return 2;
     const size_t s = h.kind == CSR5HIP_F64 ? 8 : h.kind == CSR5HIP_F32 ? 4 : 2, ws = s == 2 ? 4 : s;
     const size_t m = h.m, n = h.n, nnz = h.nnz;
@@ -259,7 +269,8 @@ int main(int argc, char **argv)
         written = outputs(h, s, ws, c);
         rc = launch(h.variant, h.mode, A, h.kind, c);
     }
-    if (h.variant == LOWP && !rc) { // the same case through the float edge launcher on operands widened here, element by element
+    if ((h.variant == LOWP || h.variant == DROP_LOWP) && !rc) { // the same case through the float edge launcher (DROP_LOWP: the float
+                                                                // dropped one) on operands widened here, element by element
         c.B = widened(h.kind, c.B, nnz * h.ldb);
         c.Q = widened(h.kind, Q, m * h.ldq) + h.offk; c.K = widened(h.kind, K, n * h.ldk) + h.offk;
         c.V = widened(h.kind, V, n * h.ldv) + h.offd;
@@ -267,7 +278,7 @@ int main(int argc, char **argv)
             c.dO = widened(h.kind, dO, m * h.ldo) + h.offd;
         for (const Block &b : outputs(h, 4, 4, c))
             written.push_back(b);
-        rc = launch(EDGE, h.mode, A, CSR5HIP_F32, c);
+        rc = launch(h.variant == LOWP ? EDGE : DROP, h.mode, A, CSR5HIP_F32, c);
     }
     f = fopen(argv[2], "wb");
     for (const Block &b : written)

@@ -26,11 +26,12 @@ MAGIC = 0x35545441
 FIELDS = ("variant", "mode", "kind", "m", "n", "nnz", "sigma", "p", "sigma_t", "p_t", "k", "d", "heads", "groups",
           "ldq", "ldk", "ldv", "ldo", "lddq", "lddk", "lddv", "ldb", "lddb", "lddar", "ldm", "want",
           "has_b", "has_a", "has_slopes", "has_values", "has_map", "head0", "offk", "offd")
-PLAIN, BIASED, EDGE, LOWP, GAT, DROP, DROP_GAT = range(7)
+PLAIN, BIASED, EDGE, LOWP, GAT, DROP, DROP_GAT, DROP_LOWP = range(8)
+SIXTEEN = (LOWP, DROP_LOWP)  # the variants whose case runs twice: the 16-bit call, then the float launcher on the widened operands
 FORWARD, BACKWARD, MASK = range(3)
 KIND = {"float64": 0, "float32": 1, "bf16": 2, "f16": 3}
 # csr5_<unit>.hip, forward and backward of the variants in their order; the all-units program links too, and takes a minute to compile
-ALL_UNITS = tuple("attention" + d + v for v in ("", "_bias", "_edge", "_lowp", "_gat", "_drop", "_drop_gat") for d in ("", "_bwd"))
+ALL_UNITS = tuple("attention" + d + v for v in ("", "_bias", "_edge", "_lowp", "_gat", "_drop", "_drop_gat", "_drop_lowp") for d in ("", "_bwd"))
 
 CONFIGS = ((4, 16, False, 0), (7, 4, True, 1), (16, 7, False, 1))  # sigma, the companion's sigma, padded, head groups (0: the rule)
 SCALE = 0.37
@@ -187,7 +188,7 @@ def launch(exe, tmp, variant, mode, pat, sigmas, ops, pad=False, groups=0, want=
     "f16" -- the words of that type; scalars: scale, negative slope, p, seed, offset; single = h: the call with heads = 1 on head
     h's slices of the same packed rows.  Every padding element is NaN.
     FORWARD: O (m, H, d).  BACKWARD: ([dQ, dK, dV, dB, dAr] as far as the variant has them, None where not wanted; the workspace
-    (m, heads, 4)).  MASK: (nnz, ldm) bytes.  LOWP: two of these, the call's own in words and the float edge launcher's."""
+    (m, heads, 4)).  MASK: (nnz, ldm) bytes.  LOWP and DROP_LOWP: two of these, the call's own in words and the float (edge, dropped) launcher's."""
     mat = pat.mat
     Q, V = ops[0], ops[2]
     (_, H, k), d, dtype = Q.shape, V.shape[2], Q.dtype
@@ -247,7 +248,7 @@ def launch(exe, tmp, variant, mode, pat, sigmas, ops, pad=False, groups=0, want=
             return np.ascontiguousarray(g[:, :width]).reshape(shape)
         assert poison(g).all(), "an output that was not wanted is written"
         return None
-    for dt in (dtype, np.dtype(np.float32)) if variant == LOWP else (dtype,):
+    for dt in (dtype, np.dtype(np.float32)) if variant in SIXTEEN else (dtype,):
         if mode == FORWARD:
             sets.append(take(dt, mat.m, h["ldo"], wd, (mat.m, H, d)))
             continue
@@ -256,10 +257,10 @@ def launch(exe, tmp, variant, mode, pat, sigmas, ops, pad=False, groups=0, want=
         for b in bits:
             rows, ld, width = shapes[b]
             outs.append(take(dt, rows, h[ld], H * width, (rows, H) + ((width,) if b != 8 else ()), want & b))
-        work = take(np.dtype(np.float32) if variant == LOWP else dt, 4 * mat.m * h["heads"], 1, 1, (mat.m, h["heads"], 4), want & 6)
+        work = take(np.dtype(np.float32) if variant in SIXTEEN else dt, 4 * mat.m * h["heads"], 1, 1, (mat.m, h["heads"], 4), want & 6)
         sets.append((outs, work))
     assert at == raw.size
-    return sets if variant == LOWP else sets[0]
+    return sets if variant in SIXTEEN else sets[0]
 
 
 def arguments(matrices, heads=None, kd=None, kinds="dtypes", extra=()):

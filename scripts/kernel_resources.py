@@ -2,7 +2,7 @@
 """Resource table of the SpMV kernels from hipcc's own -Rpass-analysis=kernel-resource-usage remarks.
 
     python scripts/kernel_resources.py [--filter k_spmv] [--sigmas few|all] [--units 'attention_(bwd_)?edge'] > profiles/rNN_resources.md
-Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_attention_edge.hip, csr5_attention_bwd_edge.hip, csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip, csr5_attention_gat.hip, csr5_attention_bwd_gat.hip, csr5_attention_drop.hip, csr5_attention_drop_gat.hip, csr5_attention_bwd_drop.hip, csr5_attention_bwd_drop_gat.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
+Compiles csr5_spmv.hip, csr5_spmm.hip, csr5_sddmm.hip, csr5_softmax.hip, csr5_attention.hip, csr5_attention_bwd.hip, csr5_attention_bias.hip, csr5_attention_bwd_bias.hip, csr5_attention_edge.hip, csr5_attention_bwd_edge.hip, csr5_attention_lowp.hip, csr5_attention_bwd_lowp.hip, csr5_attention_gat.hip, csr5_attention_bwd_gat.hip, csr5_attention_drop.hip, csr5_attention_drop_gat.hip, csr5_attention_bwd_drop.hip, csr5_attention_bwd_drop_gat.hip, csr5_attention_drop_lowp.hip, csr5_attention_bwd_drop_lowp.hip, csr5_slab.hip, csr5_hot.hip, csr5_refresh.hip and csr5_companion.hip for gfx950 with the remark pass on and prints, per kernel instantiation,
 VGPRs / SGPRs / scratch / LDS / occupancy in waves per SIMD.  --units compiles only the translation units whose file name matches.
 Runs without a GPU."""
 import argparse
@@ -53,6 +53,9 @@ def main():
                       ("csr5_attention_bwd_drop.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
                       ("csr5_attention_bwd_drop_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F64"]),
                       ("csr5_attention_bwd_drop_gat.hip", ["-DCSR5_ATTENTION_BWD_ONLY_F32"]),
+                      ("csr5_attention_drop_lowp.hip", ["-DCSR5_LOWP_ONLY_BF16"]), ("csr5_attention_drop_lowp.hip", ["-DCSR5_LOWP_ONLY_F16"]),
+                      ("csr5_attention_bwd_drop_lowp.hip", ["-DCSR5_LOWP_ONLY_BF16"]),
+                      ("csr5_attention_bwd_drop_lowp.hip", ["-DCSR5_LOWP_ONLY_F16"]),
                       ("csr5_slab.hip", []), ("csr5_hot.hip", []),
                       ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F64"]), ("csr5_refresh.hip", ["-DCSR5_REFRESH_ONLY_F32"]),
                       ("csr5_companion.hip", [])):
