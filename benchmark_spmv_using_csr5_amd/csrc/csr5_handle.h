@@ -85,7 +85,7 @@ enum SlabBuf {
     B_ROW_PTR2, B_COL2, B_VAL2, B_VAL32, B_P, B_ROWIDX, B_BASE, B_NONEMPTY,
     B_TMP, // temporaries of the slab build; kept between conversions only while small (SLAB_TMP_KEEP)
     // LDS hot table of the slab child (k_spmv_range): chosen at conversion, see csr5_slab.hip
-    B_HOT_COLS, B_HOT_COUNT, B_HOT_TILE0, B_SLAB_OFF, B_LEAD, B_RANGE_HEAD,
+    B_HOT_COLS, B_HOT_COUNT, B_HOT_TILE0, B_SLAB_OFF, B_LEAD, B_RANGE_HEAD, B_RANGE_CUT,
     B_COL_LO, B_COL_HI, // packed column codes of a hot child (3 bytes per non-zero)
     // permuted copy of x behind the packed codes (csr5_hot.hip k_x_permute): table images + frequency-ordered cold regions
     B_COLD_BASE, B_COLD_COLS, B_XPERM,

@@ -13,8 +13,11 @@
 //     stores of a wavefront are sequential over its whole range.
 // Round 2's form (tiles dealt round robin, per-tile 32-byte header, short-spill re-reads, arrival protocol) is gone.
 #include "csr5_internal.h"
+#include "csr5_range_cut.h"
 #include "csr5_slabmap.h"
 #include "csr5_wave.h"
+
+#include <rocprim/device/device_scan.hpp>
 
 #include <type_traits>
 
@@ -23,29 +26,12 @@ namespace csr5 {
 constexpr int HOT_BLOCK = HOT_WAVES * OMEGA;
 
 // ---- which tiles of a slab does wavefront range rho walk? ------------------------------------------------------------------
-// The slab's n tiles are dealt evenly to the workgroups (HOT_WAVES ranges each); inside a workgroup the wavefronts do NOT get
-// equal shares.  With two wavefronts per SIMD the one that was launched first wins every issue conflict: measured with
-// wall-clock stamps per range (scripts/experiments/round5/range_stamps.py, R-MAT 24) wavefronts 0-3 of a workgroup finish
-// equal ranges 5.5 % below the mean and wavefronts 4-7 5.5 % above it, in every workgroup and slab (with a skew of 80 per mille: 0.98 ... 1.016) -- and the workgroup waits
-// for its slowest wavefront at every slab boundary (the table refill).  The first half of a workgroup's wavefronts therefore
-// takes HOT_SKEW_PERMIL per mille more tiles than the mean, the second half as much less.
-#ifndef CSR5_HOT_SKEW_PERMIL
-#define CSR5_HOT_SKEW_PERMIL 85
-#endif
-constexpr int HOT_SKEW_PERMIL = HOT_WAVES == 8 ? CSR5_HOT_SKEW_PERMIL : 0;
-__host__ __device__ __forceinline__ int hot_range_begin(int n, int rho) // first tile (relative to the slab) of range rho; rho == ranges: n
-{
-    constexpr int nwg = HOT_RANGES_PER_SLAB / HOT_WAVES;
-    const int wg = rho / HOT_WAVES, j = rho % HOT_WAVES;
-    if (wg >= nwg)
-        return n;
-    const int q = n / nwg, rem = n % nwg;
-    const int wb = wg * q + (wg < rem ? wg : rem), sz = q + (wg < rem ? 1 : 0);
-    // cumulative share of wavefronts 0 .. j-1 in 1/(1000 HOT_WAVES): 1000 + skew each in the first half, 1000 - skew in the second
-    constexpr int half = HOT_WAVES / 2;
-    const int cum = j <= half ? j * (1000 + HOT_SKEW_PERMIL) : half * (1000 + HOT_SKEW_PERMIL) + (j - half) * (1000 - HOT_SKEW_PERMIL);
-    return wb + (int)((long long)sz * cum / (1000 * HOT_WAVES));
-}
+// Tiles range_begin[slab][rho] .. range_begin[slab][rho + 1] - 1 (DeviceArrays::range_begin: absolute tile numbers, 257 words
+// per slab), a table made at conversion by k_range_cuts below with the rule of csr5_range_cut.h: the slab's modelled cost --
+// not its tile count -- is dealt evenly to the workgroups, and inside a workgroup the wavefronts that were launched first take
+// more of it (they win every issue conflict: profiles/r05_probes.txt section 2).  The workgroup waits for its slowest
+// wavefront at every slab boundary (the table refill), and the kernel ends with its slowest workgroup.
+static_assert(CUT_RANGES == HOT_RANGES_PER_SLAB && CUT_WAVES == HOT_WAVES, "csr5_range_cut.h restates the shape of the range kernel");
 
 // The child's column words come as 3-byte codes (k_hot_encode ENC_PACK) in CSR order -- lane l's sigma codes are
 // consecutive: 2 sigma bytes of col_lo, sigma bytes of col_hi (whole dwords: the child's sigma is a multiple of four) --
@@ -126,6 +112,18 @@ extern "C" int csr5hip_debug_range_stamps(unsigned long long *dst, int count)
 {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_range_stamps), (size_t)count * sizeof(unsigned long long));
 }
+// ... and what the last conversion's cut pass saw and made: cold lanes | row starts << 16 of the first 2^20 tiles, the cut table
+constexpr int STAMP_TILES = 1 << 20;
+__device__ unsigned g_tile_stats[STAMP_TILES];
+__device__ int g_cut_table[64 * CUT_TABLE_STRIDE];
+extern "C" int csr5hip_debug_tile_stats(unsigned *dst, int count)
+{
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tile_stats), (size_t)(count < STAMP_TILES ? count : STAMP_TILES) * sizeof(unsigned));
+}
+extern "C" int csr5hip_debug_cut_table(int *dst, int count)
+{
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_cut_table), (size_t)(count < 64 * CUT_TABLE_STRIDE ? count : 64 * CUT_TABLE_STRIDE) * sizeof(int));
+}
 #endif
 
 template <typename VT, int SIGMA, bool NT, int DEPTH, typename ST = VT>
@@ -172,11 +170,12 @@ k_spmv_range(Geometry g, const ST *__restrict__ val, const uint32_t *__restrict_
         }
         __syncthreads();
 
-        // this wavefront's contiguous range of the slab's tiles
-        const int t0 = hp.tile0[k], n = hp.tile0[k + 1] - t0;
+        // this wavefront's contiguous range of the slab's tiles: two neighbouring words of the cut table, wave-uniform -- through
+        // the scalar cache like the tile_ptr pairs
         const int nr = nwg * (HOT_BLOCK / OMEGA), rho = wg * (HOT_BLOCK / OMEGA) + wave;
-        const int tb = __builtin_amdgcn_readfirstlane(t0 + hot_range_begin(n, rho));
-        const int te = __builtin_amdgcn_readfirstlane(t0 + hot_range_begin(n, rho + 1));
+        const auto *cut = (const __attribute__((address_space(4))) int32_t *)(uintptr_t)hp.range_begin;
+        const int at = __builtin_amdgcn_readfirstlane(k * CUT_TABLE_STRIDE + rho);
+        const int tb = cut[at], te = cut[at + 1];
         VT *const my_lead = lead + (size_t)k * nr + rho;
 #if defined(CSR5_RANGE_STAMPS)
         if (lane == 0)
@@ -467,15 +466,14 @@ struct RangeHead {
     int row;            // first row of the range, -1 = the range holds no tile
     long long first;    // index of its first element
 };
-__device__ __forceinline__ RangeHead range_head(const Geometry &g, const int32_t *__restrict__ tile0,
+__device__ __forceinline__ RangeHead range_head(const Geometry &g, const int32_t *__restrict__ range_begin,
                                                 const uint32_t *__restrict__ tile_ptr, int R, int nranges, int ranges_per_slab)
 {
     if (R >= nranges)
         return RangeHead{g.tail_start < g.m ? g.tail_start : -1, (long long)(g.p - 1) * g.tile_elems};
     const int k = R / ranges_per_slab, rho = R % ranges_per_slab;
-    const int t0 = tile0[k], n = tile0[k + 1] - t0;
-    const int tb = t0 + hot_range_begin(n, rho);
-    if (hot_range_begin(n, rho + 1) - hot_range_begin(n, rho) <= 0)
+    const int tb = range_begin[k * CUT_TABLE_STRIDE + rho];
+    if (range_begin[k * CUT_TABLE_STRIDE + rho + 1] <= tb)
         return RangeHead{-1, 0};
     return RangeHead{(int)(tile_ptr[tb] & ROW_MASK), (long long)tb * g.tile_elems};
 }
@@ -483,11 +481,11 @@ __device__ __forceinline__ RangeHead range_head(const Geometry &g, const int32_t
 // conversion time, ONE workgroup: head[R] = first row of range R | RANGE_EXACT, for R = 0 .. nranges (the tail); a range
 // without tiles takes the word of the next range that has some (its lead is 0: it joins that range's run, or leads it)
 __global__ void __launch_bounds__(1024)
-k_range_heads(Geometry g, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ tile0,
+k_range_heads(Geometry g, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ range_begin,
               const uint32_t *__restrict__ tile_ptr, int nranges, int ranges_per_slab, uint32_t *__restrict__ head)
 {
     for (int R = threadIdx.x; R <= nranges; R += 1024) {
-        const RangeHead h = range_head(g, tile0, tile_ptr, R, nranges, ranges_per_slab);
+        const RangeHead h = range_head(g, range_begin, tile_ptr, R, nranges, ranges_per_slab);
         head[R] = h.row < 0 ? 0xFFFFFFFFu : ((uint32_t)h.row | ((long long)row_ptr[h.row] == h.first ? RANGE_EXACT : 0u));
     }
     __threadfence_block();
@@ -745,8 +743,8 @@ hipError_t launch_narrow(const double *v, size_t n, float *o, int tile_elems, in
 template <typename VT, int SIGMA, bool NT, typename ST = VT>
 static hipError_t launch_range(const Geometry &g, const DeviceArrays &d, const void *x, void *y, hipStream_t s, bool prepare_only)
 {
-    HotParams hp{d.hot_slabs, d.hot_slabs / NUM_XCD, d.hot_capacity, d.hot_count, d.hot_tile0, d.col_lo,
-                 d.col_hi,    d.slab_off,             d.xperm,        d.cold_base, d.cold_total};
+    HotParams hp{d.hot_slabs, d.hot_slabs / NUM_XCD, d.hot_capacity, d.hot_count,  d.hot_tile0,  d.col_lo,
+                 d.col_hi,    d.slab_off,             d.xperm,        d.cold_base, d.cold_total, d.range_begin};
     const size_t lds = (size_t)d.hot_capacity * sizeof(VT) + (size_t)HOT_WAVES * HOT_WAVE_LDS;
     constexpr int DEPTH = CSR5_HOT_DEPTH;
     if constexpr (std::is_same<VT, double>::value && std::is_same<ST, double>::value) {
@@ -774,12 +772,99 @@ static hipError_t launch_range(const Geometry &g, const DeviceArrays &d, const v
     return hipGetLastError();
 }
 
+// ---- conversion time: the cut table (csr5_range_cut.h) ------------------------------------------------------------------------
+// One wavefront per tile of the hot child, tiles 0 .. tiles-1: E[t + 1] = cost of tile t from the HIGH bytes of its packed column
+// codes -- bit 23 (clear: a cold lane) and bit 22 (set: a row start) of a code are bits 7 and 6 of its col_hi byte, so the pass
+// reads one byte per non-zero, 16 of them per lane and load.  E[0] = 0; an inclusive scan turns E into the prefix costs.
+__global__ void __launch_bounds__(256)
+k_tile_cost(int tiles, int T, const uint8_t *__restrict__ col_hi, unsigned long long *__restrict__ E)
+{
+    const int lane = threadIdx.x & (OMEGA - 1);
+    const int t = blockIdx.x * (256 / OMEGA) + (int)(threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        E[0] = 0;
+    if (t >= tiles)
+        return;
+    const u32x4 *hi = reinterpret_cast<const u32x4 *>(col_hi + (size_t)t * T); // (T is a multiple of 64 OMEGA ... of 16)
+    int hot = 0, starts = 0;
+    for (int q = lane; q < T / 16; q += OMEGA) {
+        const u32x4 w = hi[q];
+        hot += __builtin_popcount(w.x & 0x80808080u) + __builtin_popcount(w.y & 0x80808080u) +
+               __builtin_popcount(w.z & 0x80808080u) + __builtin_popcount(w.w & 0x80808080u);
+        starts += __builtin_popcount(w.x & 0x40404040u) + __builtin_popcount(w.y & 0x40404040u) +
+                  __builtin_popcount(w.z & 0x40404040u) + __builtin_popcount(w.w & 0x40404040u);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        hot += __shfl_xor(hot, d, OMEGA);
+        starts += __shfl_xor(starts, d, OMEGA);
+    }
+    if (lane == 0)
+        E[t + 1] = range_tile_cost(T, T - hot, starts);
+#if defined(CSR5_RANGE_STAMPS)
+    if (lane == 0 && t < STAMP_TILES)
+        g_tile_stats[t] = (unsigned)(T - hot) | (unsigned)starts << 16;
+#endif
+}
+
+// workgroup k = slab k: range_begin[k][0 .. 256] (absolute tile numbers) from the prefix costs
+__global__ void __launch_bounds__(320)
+k_range_cuts(int S, const int32_t *__restrict__ tile0, const unsigned long long *__restrict__ E, int32_t *__restrict__ range_begin)
+{
+    const int k = blockIdx.x, rho = threadIdx.x;
+    const int t0 = tile0[k], n = tile0[k + 1] - t0;
+    const uint64_t *Ek = reinterpret_cast<const uint64_t *>(E) + t0;
+    if (rho <= CUT_RANGES)
+        range_begin[k * CUT_TABLE_STRIDE + rho] = t0 + range_cut_begin(Ek, n, rho, RANGE_SLOTS_DEFAULT);
+#if defined(CSR5_RANGE_STAMPS)
+    if (rho <= CUT_RANGES && k < 64)
+        g_cut_table[k * CUT_TABLE_STRIDE + rho] = t0 + range_cut_begin(Ek, n, rho, RANGE_SLOTS_DEFAULT);
+#endif
+}
+
+// what the cut table's buffer holds: [S][257] int32 | [tiles + 1] prefix costs | the scan's scratch
+static size_t cut_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t cut_scan_bytes(int tiles)
+{
+    size_t bytes = 0;
+    unsigned long long *nu = nullptr;
+    (void)rocprim::inclusive_scan(nullptr, bytes, nu, nu, (size_t)(tiles > 0 ? tiles : 1), rocprim::plus<unsigned long long>(), nullptr);
+    return bytes;
+}
+RangeCutLayout range_cut_layout(int S, int tiles)
+{
+    RangeCutLayout l{};
+    l.prefix = cut_align((size_t)S * CUT_TABLE_STRIDE * 4);
+    l.scan = l.prefix + cut_align(((size_t)(tiles > 0 ? tiles : 0) + 1) * 8);
+    l.scan_bytes = cut_scan_bytes(tiles);
+    l.total = l.scan + cut_align(l.scan_bytes);
+    return l;
+}
+// tiles = the child's tiles without its CSR tail (tile0[S]); T = its tile size; buf = range_cut_layout(S, tiles).total bytes
+hipError_t launch_range_cuts(int S, int tiles, int T, const int32_t *tile0, const uint8_t *col_hi, void *buf, hipStream_t s)
+{
+    const RangeCutLayout l = range_cut_layout(S, tiles);
+    auto *E = reinterpret_cast<unsigned long long *>((char *)buf + l.prefix);
+    hipLaunchKernelGGL(k_tile_cost, dim3((unsigned)((tiles > 0 ? tiles : 0) / (256 / OMEGA) + 1)), dim3(256), 0, s, tiles, T, col_hi, E);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    if (tiles > 0) {
+        size_t bytes = l.scan_bytes;
+        e = rocprim::inclusive_scan((char *)buf + l.scan, bytes, E + 1, E + 1, (size_t)tiles, rocprim::plus<unsigned long long>(), s);
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_range_cuts, dim3(S), dim3(320), 0, s, S, tile0, E, reinterpret_cast<int32_t *>(buf));
+    return hipGetLastError();
+}
+
 // conversion time (after the child's tile_ptr exists): which row every wavefront range starts in
 hipError_t launch_range_heads(const Geometry &g, const DeviceArrays &d, hipStream_t s)
 {
     if (g.p <= 0)
         return hipSuccess;
-    hipLaunchKernelGGL(k_range_heads, dim3(1), dim3(1024), 0, s, g, d.row_ptr, d.hot_tile0, d.tile_ptr,
+    hipLaunchKernelGGL(k_range_heads, dim3(1), dim3(1024), 0, s, g, d.row_ptr, d.range_begin, d.tile_ptr,
                        d.hot_slabs * HOT_RANGES_PER_SLAB, HOT_RANGES_PER_SLAB, d.range_head);
     return hipGetLastError();
 }
@@ -790,7 +875,7 @@ template <typename VT>
 static hipError_t launch_range_sigma(const Geometry &g, const DeviceArrays &d, const void *x, void *y, bool nt, hipStream_t s,
                                      bool prepare_only)
 {
-    if (!d.col_lo || !d.xperm)
+    if (!d.col_lo || !d.xperm || !d.range_begin)
         return hipErrorInvalidValue;
     switch (g.sigma) {
 #define CSR5_HOT_CASE(S)                                                                                               \

@@ -79,6 +79,8 @@ struct DeviceArrays {
     int hot_slabs, hot_capacity;
     void *range_lead;          // [hot_slabs * HOT_RANGES_PER_SLAB] of vT: leading partial of every wavefront range (csr5_hot.hip)
     uint32_t *range_head;      // [hot_slabs * HOT_RANGES_PER_SLAB + 1] first row of every range (+ the CSR tail), k_range_heads
+    const int32_t *range_begin; // [hot_slabs][HOT_RANGES_PER_SLAB + 1] first tile of every range, cut by modelled cost (csr5_range_cut.h,
+                               // k_range_cuts); behind it in the same buffer: the tiles' prefix costs (RangeCutLayout)
     // packed column codes of a hot child (k_hot_encode ENC_PACK): 3 bytes per non-zero in the child's CSR order
     const uint16_t *col_lo;
     const uint8_t *col_hi;
@@ -225,6 +227,7 @@ struct HotParams {
     const void *xp;                  // permuted copy of x (DeviceArrays::xperm)
     const int32_t *cold_base;
     int cold_total;
+    const int32_t *range_begin;      // [slabs][257] first tile of every wavefront range (DeviceArrays::range_begin)
 };
 // sigma of a hot slab child: a tile's values fill the y-compaction region exactly (8 for fp64, 16 for fp32: multiples of four,
 // so a lane's 3-byte column codes are whole dwords), whatever the parent's sigma.  Measured: the hot kernel is flat in sigma
@@ -343,6 +346,14 @@ hipError_t prepare_spmv_hot(const Geometry &g, const DeviceArrays &d, int value_
 hipError_t launch_fp32_exact(const double *v, size_t n, unsigned *flag, hipStream_t s);
 hipError_t launch_narrow(const double *v, size_t n, float *o, int tile_elems, int transposed_tiles, hipStream_t s);
 hipError_t launch_range_heads(const Geometry &g, const DeviceArrays &d, hipStream_t s);
+// the cut table of a hot child (csr5_range_cut.h) from its packed column codes, one buffer: byte offsets of its parts
+struct RangeCutLayout {
+    size_t prefix;     // [tiles + 1] uint64: cost of the tiles in front of every tile (the table itself, [S][257] int32, sits at offset 0)
+    size_t scan, scan_bytes; // the prefix scan's scratch
+    size_t total;
+};
+RangeCutLayout range_cut_layout(int S, int tiles);
+hipError_t launch_range_cuts(int S, int tiles, int T, const int32_t *tile0, const uint8_t *col_hi, void *buf, hipStream_t s);
 // the permuted copy of x behind the packed codes of a hot child: xperm[i] = x[hot_cols[i]] for the table images,
 // xperm[slabs * capacity + i] = x[cold_cols[i]] for the cold region
 hipError_t launch_x_permute(const Geometry &g, const DeviceArrays &d, int value_type, const void *x, hipStream_t s);

@@ -771,57 +771,94 @@ k_hot_threshold(int capacity, int min_count, const uint32_t *__restrict__ chist,
     }
 }
 
-// Every column with count >= thr is marked hot; columns of the next lower count fill the room that is left (thr[S + k],
-// from k_hot_threshold), first come first served.  A workgroup walks HOT_ASSIGN_COLS columns twice: first it counts the
-// second-class columns it wants per slab (LDS), reserves them with ONE global add per slab, then hands them out from LDS
-// counters (196 k adds on 16 words -- one per chosen column -- took 0.9 ms on R-MAT 24).  The bitmap only says WHETHER a
-// column gets a slot; k_hot_rank numbers them.
+// Every column with count >= thr is marked hot; columns of the next lower count -- the second class -- fill the room that is left
+// (thr[S + k], from k_hot_threshold).  WHICH of them must not depend on the order in which workgroups run: the range kernel's
+// ranges are cut by the tiles' cold lanes (csr5_range_cut.h), so the table's content decides in which association a row that
+// straddles a cut is added, and the same matrix must give the same bits after every conversion.  The second class is therefore
+// taken in the order of a hash of the column: a histogram of the hashes per slab (k_hot_hist2, in the buckets k_hot_threshold has
+// read), the number of leading hash buckets whose columns all fit (k_hot_cutoff, into thr[S + k]), and k_hot_assign takes the
+// columns in front of that cut -- at most one bucket's columns (a 2 048th of the class) fewer than the room holds.
+__host__ __device__ inline uint32_t hot_hash(uint32_t c) { return (c * 2654435761u) >> 21; } // 11 bits: HOT_BUCKETS
+static_assert(HOT_BUCKETS == 1 << 11, "hot_hash yields a bucket");
+// 0 = not chosen, 1 = first class (count >= thr), 2 = second class (count == thr - 1)
+__device__ __forceinline__ int hot_class(uint32_t v, uint32_t b, int min_count)
+{
+    if (!v)
+        return 0;
+    const uint32_t bucket = v < HOT_BUCKETS - 1 ? v : HOT_BUCKETS - 1;
+    return bucket >= b ? 1 : (bucket + 1 == b && (int)bucket >= min_count ? 2 : 0);
+}
+__global__ void __launch_bounds__(SLAB_BLOCK)
+k_hot_hist2(int n, const uint32_t *__restrict__ cnt, int bits, int shift, const uint32_t *__restrict__ thr, int min_count,
+            uint32_t *__restrict__ hist2)
+{
+    const int first = blockIdx.x * HOT_HIST_COLS;
+    for (int c = first + threadIdx.x; c < first + HOT_HIST_COLS && c < n; c += SLAB_BLOCK) {
+        const uint32_t k = slab_of((uint32_t)c, shift, bits);
+        if (hot_class(cnt[c], thr[k], min_count) == 2)
+            atomicAdd(&hist2[(size_t)k * HOT_BUCKETS + hot_hash((uint32_t)c)], 1u);
+    }
+}
+// one wavefront per slab: thr[S + k] = room -> the number of leading hash buckets whose second-class columns fit the room together
+__global__ void __launch_bounds__(OMEGA)
+k_hot_cutoff(const uint32_t *__restrict__ hist2, uint32_t *__restrict__ thr)
+{
+    constexpr int PER = HOT_BUCKETS / OMEGA;
+    const int lane = threadIdx.x;
+    const uint32_t *h = hist2 + (size_t)blockIdx.x * HOT_BUCKETS + lane * PER;
+    const unsigned long long room = thr[gridDim.x + blockIdx.x];
+    uint32_t v[PER];
+    unsigned long long own = 0;
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+        v[i] = h[i];
+        own += v[i];
+    }
+    unsigned long long incl = own; // inclusive prefix over the lanes
+#pragma unroll
+    for (int d = 1; d < OMEGA; d <<= 1) {
+        const unsigned long long o = __shfl_up(incl, d, OMEGA);
+        if (lane >= d)
+            incl += o;
+    }
+    unsigned long long run = incl - own;
+    int take = 0; // buckets 0 .. take-1 fit (the prefix only grows: the fitting buckets are the leading ones)
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+        run += v[i];
+        if (run <= room)
+            take = lane * PER + i + 1;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int o = __shfl_xor(take, d, OMEGA);
+        take = o > take ? o : take;
+    }
+    __syncthreads(); // (every lane has read the room)
+    if (lane == 0)
+        thr[gridDim.x + blockIdx.x] = (uint32_t)take;
+}
+// The bitmap only says WHETHER a column gets a slot; k_hot_rank numbers them.
 constexpr int HOT_ASSIGN_COLS = 16384;
 __global__ void __launch_bounds__(SLAB_BLOCK)
 k_hot_assign(int n, int S, const uint32_t *__restrict__ cnt, int bits, int shift, const uint32_t *__restrict__ thr,
-             int min_count, int32_t *__restrict__ fill, uint32_t *__restrict__ hotbits, size_t G,
-             unsigned long long *__restrict__ covered)
+             int min_count, uint32_t *__restrict__ hotbits, size_t G, unsigned long long *__restrict__ covered)
 {
-    __shared__ int want[SLAB_MAX], base[SLAB_MAX], given[SLAB_MAX];
-    if (threadIdx.x < SLAB_MAX)
-        want[threadIdx.x] = given[threadIdx.x] = base[threadIdx.x] = 0;
-    __syncthreads();
     const int first = blockIdx.x * HOT_ASSIGN_COLS;
     const int last = first + HOT_ASSIGN_COLS < n ? first + HOT_ASSIGN_COLS : n;
-    // 0 = not chosen, 1 = first class (count >= thr), 2 = second class (count == thr - 1)
-    auto chosen = [&](int c, uint32_t &k, uint32_t &v) -> int {
-        v = cnt[c];
-        if (!v)
-            return 0;
-        k = slab_of((uint32_t)c, shift, bits);
-        const uint32_t bucket = v < HOT_BUCKETS - 1 ? v : HOT_BUCKETS - 1;
-        const uint32_t b = thr[k];
-        return bucket >= b ? 1 : (bucket + 1 == b && (int)bucket >= min_count ? 2 : 0);
-    };
-    auto mark = [&](int c, uint32_t k) {
-        const uint32_t local = slab_local((uint32_t)c, shift, bits);
-        atomicOr(&hotbits[(size_t)k * G * 4 + (local >> 5)], 1u << (local & 31));
-    };
-    uint32_t k = 0, v = 0;
     unsigned long long got = 0;
     for (int c = first + (int)threadIdx.x; c < last; c += SLAB_BLOCK) {
-        const int cls = chosen(c, k, v);
-        if (cls == 1) {
-            mark(c, k);
+        const uint32_t v = cnt[c];
+        if (!v)
+            continue;
+        const uint32_t k = slab_of((uint32_t)c, shift, bits);
+        const int cls = hot_class(v, thr[k], min_count);
+        if (cls == 1 || (cls == 2 && hot_hash((uint32_t)c) < thr[S + k])) {
+            const uint32_t local = slab_local((uint32_t)c, shift, bits);
+            atomicOr(&hotbits[(size_t)k * G * 4 + (local >> 5)], 1u << (local & 31));
             got += v;
-        } else if (cls == 2) {
-            atomicAdd(&want[k], 1);
         }
     }
-    __syncthreads();
-    if (threadIdx.x < SLAB_MAX && want[threadIdx.x])
-        base[threadIdx.x] = atomicAdd(&fill[threadIdx.x], want[threadIdx.x]);
-    __syncthreads();
-    for (int c = first + (int)threadIdx.x; c < last; c += SLAB_BLOCK)
-        if (chosen(c, k, v) == 2 && want[k] && base[k] + atomicAdd(&given[k], 1) < (int)thr[S + k]) {
-            mark(c, k);
-            got += v;
-        }
     // sampled non-zeros that found a slot: one increment per wavefront
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1)
@@ -1242,17 +1279,20 @@ hipError_t slab_hot_select(int n, int nnz, int S, int bits, int shift, int capac
                                         (int)count_lds);
     if (ea != hipSuccess)
         return ea;
-    // hot_count doubles as the fill counter of the second-class columns until k_hot_rank writes the slot counts
-    // (slot 0 of every table is reserved -- it holds +0.0, see k_spmv_range -- so those start at 1)
-    hipError_t e = hipMemsetAsync(hot_count, 0, (size_t)S * 4, s);
-    if (e != hipSuccess)
-        return e;
+    hipError_t e = hipSuccess;
     hipLaunchKernelGGL(k_col_count, dim3((unsigned)blocks), dim3(COUNT_BLOCK), count_lds, s, nnz, sample_stride, col, cnt);
     hipLaunchKernelGGL(k_hot_hist, dim3((n + HOT_HIST_COLS - 1) / HOT_HIST_COLS), dim3(SLAB_BLOCK), 0, s, n, cnt, S, bits, shift,
                        chist);
     hipLaunchKernelGGL(k_hot_threshold, dim3(S), dim3(OMEGA), 0, s, capacity, min_count, chist, thr);
+    // which columns of the second class get the room that is left: by hash order, in the buckets the threshold has read
+    e = hipMemsetAsync(chist, 0, (size_t)S * HOT_BUCKETS * 4, s);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_hot_hist2, dim3((n + HOT_HIST_COLS - 1) / HOT_HIST_COLS), dim3(SLAB_BLOCK), 0, s, n, cnt, bits, shift, thr,
+                       min_count, chist);
+    hipLaunchKernelGGL(k_hot_cutoff, dim3(S), dim3(OMEGA), 0, s, chist, thr);
     hipLaunchKernelGGL(k_hot_assign, dim3((n + HOT_ASSIGN_COLS - 1) / HOT_ASSIGN_COLS), dim3(SLAB_BLOCK), 0, s, n, S, cnt, bits, shift,
-                       thr, min_count, hot_count, (uint32_t *)hotbits, G, covered);
+                       thr, min_count, (uint32_t *)hotbits, G, covered);
     hipLaunchKernelGGL(k_hot_rank, dim3(S, (unsigned)((G + RANK_BLOCK - 1) / RANK_BLOCK)), dim3(RANK_BLOCK), 0, s, bits, shift,
                        capacity, G, hotbits, hotpre, hot_cols, hot_count);
     return hipGetLastError();

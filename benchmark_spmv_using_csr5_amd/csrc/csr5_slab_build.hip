@@ -186,7 +186,7 @@ int partition_segments(SlabBuild &b)
 }
 
 // with a table: the slabs dealt onto the XCDs (slab_deal), then the 3-byte column codes next to the plain words (the child's sigma
-// is a multiple of four: whole dwords per lane) and the cold regions of the permuted x
+// is a multiple of four: whole dwords per lane) and the cold regions of the permuted x, then the cut table of the range kernel
 int deal_and_pack(SlabBuild &b)
 {
     csr5hip_handle h = b.h;
@@ -216,6 +216,11 @@ int deal_and_pack(SlabBuild &b)
                           (uint16_t *)sl[B_COL_LO].ptr, (uint8_t *)sl[B_COL_HI].ptr, (uint8_t *)b.tmp(T_REF), (uint32_t *)b.tmp(T_RANK),
                           (uint32_t *)b.tmp(T_KEYS), (uint32_t *)b.tmp(T_KEYS2), (uint32_t *)b.tmp(T_SRC), b.tmp(T_SORT), b.sz.cold_sort,
                           (int32_t *)sl[B_COLD_BASE].ptr, (int32_t *)sl[B_COLD_COLS].ptr, s));
+    // the codes say what every tile costs a wavefront next to the others of its workgroup (cold lanes, row starts): every workgroup's
+    // span of a slab is cut into its wavefronts' ranges by that cost (csr5_range_cut.h)
+    const int tiles = pl.hot_p - 1;
+    HIP_TRY(sl[B_RANGE_CUT].reserve(range_cut_layout(S, tiles).total));
+    HIP_TRY(launch_range_cuts(S, tiles, pl.hot_T, (const int32_t *)sl[B_HOT_TILE0].ptr, (const uint8_t *)sl[B_COL_HI].ptr, sl[B_RANGE_CUT].ptr, s));
     HIP_TRY(hipMemcpyAsync(&cold_total, (int32_t *)sl[B_COLD_BASE].ptr + S, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s)); // (`order` is in use until here)
     sl.cold_total = cold_total;
@@ -271,6 +276,7 @@ int convert_child(SlabBuild &b)
     c->d.hot_capacity = b.plan.hot_capacity;
     c->d.range_lead = sl[B_LEAD].ptr;
     c->d.range_head = (uint32_t *)sl[B_RANGE_HEAD].ptr;
+    c->d.range_begin = hot ? (const int32_t *)sl[B_RANGE_CUT].ptr : nullptr;
     int rc = csr5hip_input_csr(c, g.nnz, (int32_t *)sl[B_ROW_PTR2].ptr, (int32_t *)sl[B_COL2].ptr, sl[B_VAL2].ptr);
     c->sigma_request = hot ? b.plan.hot_sigma : g.sigma;
     if (rc == CSR5HIP_SUCCESS)
