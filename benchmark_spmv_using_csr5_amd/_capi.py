@@ -75,6 +75,18 @@ class Csr5Info(C.Structure):
     ]
 
 
+class SlabView(C.Structure):  # csr5hip_slab_view
+    _fields_ = [
+        ("S", C.c_int), ("capacity", C.c_int), ("slab_shift", C.c_int), ("slab_bits", C.c_int),
+        ("sigma", C.c_int), ("T", C.c_int), ("p", C.c_int), ("tail_start", C.c_int), ("segments", C.c_int),
+        ("cold_total", C.c_int), ("stride", C.c_int), ("min_count", C.c_int), ("values_narrowed", C.c_int),
+        ("slab_off", C.c_void_p), ("hot_tile0", C.c_void_p), ("hot_count", C.c_void_p), ("hot_cols", C.c_void_p),
+        ("cold_base", C.c_void_p), ("cold_cols", C.c_void_p), ("col_lo", C.c_void_p), ("col_hi", C.c_void_p),
+        ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p), ("val32", C.c_void_p), ("tile_ptr", C.c_void_p),
+        ("range_begin", C.c_void_p), ("range_cost", C.c_void_p), ("range_head", C.c_void_p), ("xperm", C.c_void_p),
+    ]
+
+
 MTX_CANNOT_OPEN = -1
 MTX_BAD_BANNER = -2
 MTX_COMPLEX = -3
@@ -143,6 +155,7 @@ SYMBOLS = [
     ("csr5hip_autotune_sigma", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("csr5hip_set_option", C.c_int, [_H, C.c_int, C.c_int]),
     ("csr5hip_get_info", C.c_int, [_H, C.POINTER(Csr5Info)]),
+    ("csr5hip_get_slab_view", C.c_int, [_H, C.POINTER(SlabView)]),
     ("csr5hip_auto_sigma", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("csr5hip_last_error", C.c_char_p, []),
     ("csr5hip_version", C.c_char_p, []),

@@ -1372,6 +1372,53 @@ int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info)
     return CSR5HIP_SUCCESS;
 }
 
+// borrowed pointers of the hot slab child, for tests and inspection: nothing is launched, copied or allocated
+int csr5hip_get_slab_view(csr5hip_handle h, csr5hip_slab_view *out)
+{
+    if (!h || !out)
+        return CSR5HIP_INVALID_ARGUMENT;
+    const csr5hip_handle_s *c = h->slab.child;
+    if (h->format != CSR5HIP_FORMAT_CSR5 || h->slab.S <= 0 || !c || !c->hot_enabled) {
+        set_last_error("csr5hip_get_slab_view: the handle has no column-slab child with a hot table (csr5hip_info.slab_hot == 0)");
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    csr5hip_slab_view v{};
+    v.S = h->slab.S;
+    v.capacity = c->d.hot_capacity;
+    v.slab_shift = c->d.slab_shift;
+    v.slab_bits = c->d.slab_bits;
+    v.sigma = c->g.sigma;
+    v.T = c->g.tile_elems;
+    v.p = c->g.p;
+    v.tail_start = c->g.tail_start;
+    v.segments = c->g.m;
+    v.cold_total = c->d.cold_total;
+    v.stride = h->slab.sample_stride;
+    v.min_count = h->slab.min_count;
+    v.values_narrowed = h->slab.values_narrowed ? 1 : 0;
+    v.slab_off = c->d.slab_off;
+    v.hot_tile0 = c->d.hot_tile0;
+    v.hot_count = c->d.hot_count;
+    v.hot_cols = c->d.hot_cols;
+    v.cold_base = c->d.cold_base;
+    v.cold_cols = c->d.cold_cols;
+    v.col_lo = c->d.col_lo;
+    v.col_hi = c->d.col_hi;
+    v.row_ptr = c->d.row_ptr;
+    v.col = c->d.col;
+    v.val = c->d.val;
+    v.val32 = h->slab.values_narrowed ? c->d.val32 : nullptr;
+    v.tile_ptr = c->d.tile_ptr;
+    v.range_begin = c->d.range_begin;
+    // (the prefix costs lie behind the cut table in the same buffer)
+    v.range_cost = reinterpret_cast<const unsigned long long *>(reinterpret_cast<const char *>(c->d.range_begin) +
+                                                                range_cut_layout(v.S, v.p - 1).prefix);
+    v.range_head = c->d.range_head;
+    v.xperm = c->d.xperm;
+    *out = v;
+    return CSR5HIP_SUCCESS;
+}
+
 // ---- device shims ---------------------------------------------------------------------------
 int csr5hip_device_count(int *count)
 {

@@ -100,6 +100,7 @@ struct SlabStructure {
     int m2 = 0;
     int hot_cover_pct = 0;        // share of the non-zeros whose column got a table slot
     int cold_total = 0;           // entries of the cold region
+    int sample_stride = 1, min_count = 0; // (hot table) the column sample of the last build (csr5hip_get_slab_view reports them)
     bool values_narrowed = false;
     bool xperm_valid = false;     // (snapshot mode) the copy holds the current x
     bool fallback = false;        // the structure was wanted but could not be built: plain kernel in use

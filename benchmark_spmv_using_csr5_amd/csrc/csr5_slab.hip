@@ -631,9 +631,9 @@ k_slab_combine_persistent(int m, int tail_start, int zero_empty, int m2, const u
 // ---- hot columns of every slab (LDS table of the persistent kernel k_spmv_range, csr5_hot.hip) ---------------------
 // Power-law inputs concentrate their non-zeros on few columns: the HOT_CAPACITY most used columns of a slab (those
 // used at least `min_count` times -- a table entry is staged once per workgroup and SpMV, so a rarely used column
-// would cost more than it saves) get a slot in the slab's table and their column words are rewritten to
-// 0x80000000 | slot in the child's column_index.  Selection: per-slab histogram of the column use counts, threshold =
-// the smallest count whose columns all fit, the remaining room goes to columns of the next lower count.
+// would cost more than it saves) get a slot in the slab's table and their elements are coded 0x800000 | slot in the
+// child's 3-byte column codes (k_hot_encode; column_index stays plain).  Selection: per-slab histogram of the column use counts
+// (capped at HOT_BUCKETS - 1), threshold = the smallest count whose columns all fit, the remaining room goes to columns of the next lower count.
 constexpr int HOT_BUCKETS = 2048;
 
 // Use counts of the columns from a SAMPLE of the non-zeros: one 64-element chunk out of every `stride` (the reads stay
@@ -960,7 +960,7 @@ k_hot_rank(int bits, int shift, int capacity, size_t G, const uint4 *__restrict_
 //                selection instead and only needs to know WHICH columns to rank
 //   ENC_PACK     every column word of the tiles 0 .. p-2 is written as a 24-bit code -- low 16 bits to col_lo, high 8 bits
 //                to col_hi, both in the child's CSR order, which is already the order lane l of k_spmv_range wants (its
-//                sigma elements are consecutive there): bit 23 = table slot in bits 0..14, else the RANK of the column in
+//                sigma elements are consecutive there): bit 23 = table slot in bits 0..14 (an fp32 table has 2^15 slots: all of them), else the RANK of the column in
 //                its slab's frequency order (rank_of[slab][local id], < 2^22) = its index in the slab's cold region of
 //                the permuted copy of x (csr5_hot.hip); bit 22 = the element starts a row of the child (the bit flag of the
 //                reference's descriptor, from the segment keys).  3 bytes per non-zero instead of 4 in the SpMV's streams; col2

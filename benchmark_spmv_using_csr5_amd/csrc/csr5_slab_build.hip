@@ -371,6 +371,8 @@ int build_slabs_impl(csr5hip_handle h)
     }
     sl.S = b.choice.S;
     sl.m2 = (int)b.m2;
+    sl.sample_stride = b.plan.stride;
+    sl.min_count = b.plan.min_count;
     sl.t_slab = now_ms() - t0;
     return CSR5HIP_SUCCESS;
 }

@@ -1072,6 +1072,45 @@ class anonymouslibHandle:
             offset=self._d2h(i.d_offset, i.num_offsets, np.int32),
         )
 
+    def slab_view(self) -> _capi.SlabView:
+        """csr5hip_get_slab_view: scalars and borrowed device pointers of the hot slab child (valid until the next conversion or option
+        change); raises when the handle has none."""
+        view = _capi.SlabView()
+        err = self._lib.csr5hip_get_slab_view(self._h, C.byref(view))
+        if err:
+            raise RuntimeError(f"csr5hip_get_slab_view -> {err}: {_capi.last_error()}")
+        return view
+
+    def slab_child_arrays(self) -> dict:
+        """Host copies of what the conversion built for the hot slab child (for the structure tests).  Values come as stored: tiles
+        0 .. p-2 in lane-major 16-byte pieces, the CSR tail in CSR order; xperm holds the last x that spmv() permuted."""
+        v = self.slab_view()
+        nnz, S, tiles = self.info().nnz, v.S, v.p - 1
+        vt = np.float64 if self._vt == _capi.F64 else np.float32
+        return dict(
+            S=v.S, capacity=v.capacity, slab_shift=v.slab_shift, slab_bits=v.slab_bits, sigma=v.sigma, T=v.T, p=v.p,
+            tail_start=v.tail_start, segments=v.segments, cold_total=v.cold_total, stride=v.stride, min_count=v.min_count,
+            values_narrowed=v.values_narrowed,
+            slab_off=self._d2h(v.slab_off, S + 1, np.int32),
+            tile0=self._d2h(v.hot_tile0, S + 1, np.int32),
+            xcd_slabs=self._d2h(v.hot_tile0 + 4 * (S + 1), S, np.int32),
+            hot_count=self._d2h(v.hot_count, S, np.int32),
+            hot_cols=self._d2h(v.hot_cols, S * v.capacity, np.int32).reshape(S, v.capacity),
+            cold_base=self._d2h(v.cold_base, S + 1, np.int32),
+            cold_cols=self._d2h(v.cold_cols, v.cold_total, np.int32),
+            col_lo=self._d2h(v.col_lo, tiles * v.T, np.uint16),
+            col_hi=self._d2h(v.col_hi, tiles * v.T, np.uint8),
+            row_ptr=self._d2h(v.row_ptr, v.segments + 1, np.int32),
+            col=self._d2h(v.col, nnz, np.int32),
+            val=self._d2h(v.val, nnz, vt),
+            val32=self._d2h(v.val32, nnz, np.float32) if v.values_narrowed else None,
+            tile_ptr=self._d2h(v.tile_ptr, v.p + 1, np.uint32),
+            range_begin=self._d2h(v.range_begin, S * 257, np.int32).reshape(S, 257),
+            range_cost=self._d2h(v.range_cost, tiles + 1, np.uint64),
+            range_head=self._d2h(v.range_head, S * 256 + 1, np.uint32),
+            xperm=self._d2h(v.xperm, S * v.capacity + v.cold_total, vt),
+        )
+
     # -- checkpoint (SURVEY.md section 8 row f4) -----------------------------------------------
     def save(self, path: str) -> int:
         """Write the CSR5 state (row_ptr, tile-ordered col/val, the four format arrays) to `path`."""

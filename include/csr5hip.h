@@ -493,6 +493,45 @@ int csr5hip_autotune_sigma(csr5hip_handle h, void *d_y, int *best_sigma, double 
 
 int csr5hip_set_option(csr5hip_handle h, int option, int value);
 int csr5hip_get_info(csr5hip_handle h, csr5hip_info *info);
+
+/* Read-only view of the column-slab child WITH an LDS hot table (csr5hip_info.slab_hot == 1), for tests and inspection: what the
+ * conversion decided, array by array.  Scalars, and device pointers that are BORROWED from the handle: they stay valid until the
+ * next conversion (asCSR5, asCSR, inputCSR), the next csr5hip_set_option or csr5hip_free on this handle; copy them out with
+ * csr5hip_memcpy_d2h.  xperm holds the last x that spmv() (or csr5hip_snapshot_x) permuted.  A struct of its own: csr5hip_info's
+ * layout is mirrored by callers and does not grow for this. */
+typedef struct csr5hip_slab_view {
+    int S;                   /* slabs                                                                                   */
+    int capacity;            /* table slots per slab (slot 0 is reserved)                                               */
+    int slab_shift, slab_bits; /* slab of a column = xor of all slab_bits-wide groups of (column >> slab_shift)         */
+    int sigma, T, p;         /* the child's sigma, tile elements (64 sigma) and tiles (tile p - 1 is the CSR tail)      */
+    int tail_start;          /* first child row of the CSR tail                                                         */
+    int segments;            /* rows of the child = (row, slab) segments                                                */
+    int cold_total;          /* entries of the cold region                                                              */
+    int stride, min_count;   /* the column sample: one 64-element chunk in `stride`; uses a column needs for a slot     */
+    int values_narrowed;     /* 1 = val32 is in use (CSR5HIP_OPT_NARROW_VALUES)                                         */
+    const int32_t *slab_off;    /* [S + 1] first child element of every slab                                            */
+    const int32_t *hot_tile0;   /* [S + 1] first tile owned by every slab, then [S] the slabs of XCD 0, 1, ...           */
+    const int32_t *hot_count;   /* [S] slots in use, the reserved slot 0 included                                        */
+    const int32_t *hot_cols;    /* [S * capacity] column of every slot                                                   */
+    const int32_t *cold_base;   /* [S + 1] start of every slab's cold entries                                            */
+    const int32_t *cold_cols;   /* [cold_total] column of every cold entry                                               */
+    const uint16_t *col_lo;     /* low 16 bits of the packed column codes, child CSR order, tiles 0 .. p-2               */
+    const uint8_t *col_hi;      /* their high 8 bits: 0x80 = table slot, 0x40 = the element starts a child row           */
+    const int32_t *row_ptr;     /* [segments + 1] the child's row pointer                                                */
+    const int32_t *col;         /* [nnz] its plain column indices, CSR order                                             */
+    const void *val;            /* [nnz] its values: tiles 0 .. p-2 in lane-major 16-byte pieces, the tail in CSR order  */
+    const float *val32;         /* the same as fp32 in pieces of four (values_narrowed), else NULL                       */
+    const uint32_t *tile_ptr;   /* [p + 1]                                                                               */
+    const int32_t *range_begin; /* [S * 257] first tile of every wavefront range of every slab                           */
+    const unsigned long long *range_cost; /* [p] prefix costs of tiles 0 .. p-2 (entry 0 is 0), the cuts' input          */
+    const uint32_t *range_head; /* [S * 256 + 1] first child row of every range | 0x80000000, then the CSR tail's        */
+    const void *xperm;          /* [S * capacity] table images of x, then [cold_total] its cold region                   */
+} csr5hip_slab_view;
+/* Fills *out.  Launches nothing and allocates nothing.  Returns CSR5HIP_INVALID_ARGUMENT, with a csr5hip_last_error text and *out
+ * untouched, for null arguments and for a handle without a hot slab child: not converted, no column slabs, or
+ * csr5hip_info.slab_hot == 0. */
+int csr5hip_get_slab_view(csr5hip_handle h, csr5hip_slab_view *out);
+
 /* sigma that setSigma(AUTO) would pick for (m, nnz, value_type) on gfx950 */
 int csr5hip_auto_sigma(int m, int nnz, int value_type);
 const char *csr5hip_last_error(void);
