@@ -274,6 +274,16 @@ SYMBOLS_DROPOUT_LOWP = [
     ("csr5hip_dropout_mha_lowp_backward", C.c_int, SYMBOLS_LOWP_BACKWARD[0][2] + _DROP),
 ]
 
+# the max / min aggregation and its gradients, bound by load() like the others: op, weighted, X, ldx, k, Y, ldy, arg, ldarg; the
+# backward: weighted, X, ldx, k, dY, lddy, arg, ldarg, dX, lddx, dval.  A list of its own for SYMBOLS_BIASED's reason: the
+# declarations are in include/csr5hip_reduce.h; tests/test_spmm_reduce_host.py compares them with the exports.
+REDUCE_MAX, REDUCE_MIN = 0, 1
+SYMBOLS_REDUCE = [
+    ("csr5hip_spmm_reduce", C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("csr5hip_spmm_reduce_backward", C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_void_p]),
+]
+
 _lib = None
 
 
@@ -297,7 +307,7 @@ def load():
         pass
     lib = C.CDLL(path)
     for name, restype, argtypes in (SYMBOLS + SYMBOLS_BIASED + SYMBOLS_EDGE_BIAS + SYMBOLS_LOWP + SYMBOLS_LOWP_BACKWARD + SYMBOLS_GAT + SYMBOLS_DROPOUT
-                                    + SYMBOLS_DROPOUT_LOWP):
+                                    + SYMBOLS_DROPOUT_LOWP + SYMBOLS_REDUCE):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

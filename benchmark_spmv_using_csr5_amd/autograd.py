@@ -45,6 +45,11 @@ handle it still widens what was kept and goes through ``A.mhaEdgeBiasBackward`` 
 ``dropout_attention`` with bf16 or fp16 tensors is one ``A.dropoutMhaLowp`` forward and one ``A.dropoutMhaLowpBackward`` backward on
 either handle dtype.
 
+``spmm_reduce(A, val, X, reduce="max")`` is the max / min aggregator: ``A.spmmReduce`` forward (Y and the int32 argmax, one
+launch), ``A.spmmReduceBackward`` backward (``dval`` by a row kernel, ``dX`` by a column kernel on the transposed companion, built
+only when X needs a gradient).  With ``val`` the handle is given the values as ``spmm`` gives them; ``val=None`` aggregates
+X[col(e), :] itself and neither reads nor touches the handle's values or the record of them.
+
 Stream: every call runs on torch's current stream of X's device (``setStream`` before each call); the wrapper itself never
 synchronises.  Importing this module needs no GPU.
 """
@@ -55,7 +60,7 @@ import torch
 from . import _capi
 from .handle import anonymouslibHandle
 
-__all__ = ["spmm", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention", "gat_attention", "dropout_attention",
+__all__ = ["spmm", "spmm_reduce", "sddmm", "row_softmax", "attention", "fused_attention", "multihead_attention", "gat_attention", "dropout_attention",
            "gat_dropout_attention"]
 
 
@@ -132,6 +137,60 @@ def spmm(A, val, X):
     """Y = A X (m, k) with the values ``val`` (nnz, CSR order) on the pattern of the converted handle ``A``; differentiable in
     ``val`` and ``X`` (see the module docstring)."""
     return _Spmm.apply(A, val, X)
+
+
+class _SpmmReduce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, val, X, reduce):
+        weighted = val is not None
+        Xc = _rows_unit_stride(X.detach())
+        _on_current_stream(A, Xc.device)
+        key = None
+        if weighted:
+            val = val.detach()
+            if not val.is_contiguous():
+                val = val.contiguous()
+            key = _key(val)
+            _give_values(A, val, key)
+        Y = torch.empty((A._m, Xc.shape[1]), dtype=Xc.dtype, device=Xc.device)  # (the kernel writes every row)
+        arg = torch.empty((A._m, Xc.shape[1]), dtype=torch.int32, device=Xc.device)
+        _check(A.spmmReduce(Xc, Y, reduce, arg, weighted), "spmmReduce")
+        ctx.A, ctx.key, ctx.weighted = A, key, weighted
+        ctx.save_for_backward(arg, Xc, *((val,) if weighted else ()))
+        ctx.mark_non_differentiable(arg)
+        return Y, arg
+
+    @staticmethod
+    def backward(ctx, dY, _darg):
+        A, weighted = ctx.A, ctx.weighted
+        arg, X = ctx.saved_tensors[:2]
+        need_val, need_X = weighted and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_val = grad_X = None
+        if not (need_val or need_X):
+            return None, None, None, None
+        dY = dY.contiguous()
+        _on_current_stream(A, dY.device)
+        if need_val:
+            grad_val = torch.empty(A._nnz, dtype=dY.dtype, device=dY.device)
+        if need_X:
+            if weighted:  # (another forward may have given the handle other values: A^T must hold the forward's)
+                _give_values(A, ctx.saved_tensors[2], ctx.key)
+            _with_transpose(A)
+            grad_X = torch.empty((A._n, dY.shape[1]), dtype=dY.dtype, device=dY.device)  # (the kernel writes every row)
+        _check(A.spmmReduceBackward(X, dY, arg, grad_X, grad_val, weighted), "spmmReduceBackward")
+        return None, grad_val, grad_X, None
+
+
+def spmm_reduce(A, val, X, reduce="max", return_arg=False):
+    """Y[i, c] = max (or, ``reduce="min"``, min) over row i's stored entries e of val[e] * X[col(e), c] on the pattern of the converted
+    handle ``A``; differentiable in ``val`` (nnz, CSR order) and ``X`` (n, k).  ``val=None`` is the unweighted aggregation of
+    X[col(e), c]: the handle's values are neither touched nor read, and nothing about them is recorded.  With ``val`` the handle is
+    given the values as ``spmm`` gives them.  One launch forward (``A.spmmReduce`` into ``torch.empty``; a row without entries is 0);
+    the int32 argmax (m, k) and X are kept.  Backward is ``A.spmmReduceBackward``: the gradient flows to the winning entry alone (ties
+    go to the smaller rank); the transposed companion is built (once per conversion) only when X needs a gradient.
+    ``return_arg=True`` returns (Y, arg)."""
+    Y, arg = _SpmmReduce.apply(A, val, X, reduce)
+    return (Y, arg) if return_arg else Y
 
 
 class _Sddmm(torch.autograd.Function):

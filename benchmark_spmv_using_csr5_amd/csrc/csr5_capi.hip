@@ -455,6 +455,59 @@ int csr5hip_sddmm(csr5hip_handle h, const void *d_U, int ldu, const void *d_V, i
     return CSR5HIP_SUCCESS;
 }
 
+// Y[i, c] = max / min over row i's entries of a_e X[col(e), c] with its argmax (csr5_reduce.hip; the contract: csr5hip_reduce.h).
+// Runs on the handle's own tile structure whatever path spmv() takes; reads the pattern and, weighted, the tile-ordered values;
+// allocates nothing: enqueue-only from the first call.
+int csr5hip_spmm_reduce(csr5hip_handle h, int op, int weighted, const void *d_X, int ldx, int k, void *d_Y, int ldy, int32_t *d_arg,
+                        int ldarg)
+{
+    if (!h || (op != CSR5HIP_REDUCE_MAX && op != CSR5HIP_REDUCE_MIN) || (weighted != 0 && weighted != 1) || k < 0 || ldx < k ||
+        ldy < k || (d_arg && ldarg < k) || (k > 0 && h->g.m > 0 && (!d_X || !d_Y)))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (k == 0 || h->g.m <= 0)
+        return CSR5HIP_SUCCESS;
+    HIP_TRY(launch_spmm_reduce(h->g, h->d, h->value_type, op, weighted, d_X, ldx, k, d_Y, ldy, d_arg, ldarg, h->stream));
+    return CSR5HIP_SUCCESS;
+}
+
+// Its gradients in up to two launches: dval by a row kernel on the parent's pattern, dX by a column kernel on the transposed
+// companion's (its source map, comp[A_MAP], passed, not copied; weighted: its copy of the values).  A launch whose output is null is
+// not made.  Allocates nothing, changes nothing of the handle or of its companion: enqueue-only.
+int csr5hip_spmm_reduce_backward(csr5hip_handle h, int weighted, const void *d_X, int ldx, int k, const void *d_dY, int lddy,
+                                 const int32_t *d_arg, int ldarg, void *d_dX, int lddx, void *d_dval_csr)
+{
+    if (!h || (weighted != 0 && weighted != 1) || k < 0 || ldx < k || lddy < k || ldarg < k || lddx < k || (d_dval_csr && !weighted))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (k > 0 && h->g.m > 0 && ((d_dval_csr && !d_X) || !d_dY || !d_arg))
+        return CSR5HIP_INVALID_ARGUMENT;
+    if (h->format == CSR5HIP_FORMAT_CSR)
+        return CSR5HIP_UNSUPPORTED_CSR_SPMV;
+    if (h->format != CSR5HIP_FORMAT_CSR5)
+        return CSR5HIP_UNKOWN_FORMAT;
+    if (d_dX && !h->comp.built) {
+        g_last_error = "csr5hip_spmm_reduce_backward: dX needs the transposed companion, call csr5hip_build_transpose first";
+        return CSR5HIP_INVALID_ARGUMENT;
+    }
+    if (d_dval_csr && h->g.nnz > 0) {
+        if (k > 0 && h->g.m > 0)
+            HIP_TRY(launch_spmm_reduce_dval(h->g, h->d, h->value_type, d_X, ldx, k, d_dY, lddy, d_arg, ldarg, d_dval_csr, h->stream));
+        else // (no column to win in: every entry's chain is empty)
+            HIP_TRY(hipMemsetAsync(d_dval_csr, 0, (size_t)h->g.nnz * h->vsize(), h->stream));
+    }
+    if (d_dX && k > 0 && h->g.n > 0) {
+        if (h->g.nnz == 0 || h->g.m <= 0 || !h->comp.at || !h->comp[A_MAP].ptr) // no entries (and then no companion arrays): the zeros
+            HIP_TRY(hipMemset2DAsync(d_dX, (size_t)lddx * h->vsize(), 0, (size_t)k * h->vsize(), (size_t)h->g.n, h->stream));
+        else
+            HIP_TRY(launch_spmm_reduce_dx(h->comp.at->g, h->comp.at->d, (const uint32_t *)h->comp[A_MAP].ptr, h->value_type, weighted, k,
+                                          d_dY, lddy, d_arg, ldarg, d_dX, lddx, h->stream));
+    }
+    return CSR5HIP_SUCCESS;
+}
+
 // Softmax over the stored entries of every row, and its gradient (csr5_softmax.hip): nnz values in CSR order in, nnz out.  They read
 // row_ptr and nothing else of the handle, so CSR and CSR5 format are served alike; nothing is allocated or changed: enqueue-only.
 int csr5hip_row_softmax(csr5hip_handle h, const void *d_scores_csr, void *d_out_csr)

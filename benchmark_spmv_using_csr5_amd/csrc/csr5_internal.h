@@ -250,6 +250,15 @@ hipError_t launch_sddmm(const Geometry &g, const DeviceArrays &d, int value_type
 hipError_t launch_row_softmax(int m, const int32_t *row_ptr, int value_type, const void *scores, void *out, hipStream_t s);
 hipError_t launch_row_softmax_grad(int m, const int32_t *row_ptr, int value_type, const void *p, const void *g, void *out,
                                    hipStream_t s);
+// csr5_reduce.hip: the element-wise maximum / minimum over a row's entries with its argmax, and the two gradients (the contract:
+// include/csr5hip_reduce.h).  The forward and dval walk the parent's pattern (g, d: CSR5 form; d.val only when weighted); dx walks
+// the transposed companion's (gt, dt) with its source map.  No workspace; arg may be null in the forward
+hipError_t launch_spmm_reduce(const Geometry &g, const DeviceArrays &d, int value_type, int op, int weighted, const void *X, int ldx,
+                              int k, void *Y, int ldy, int32_t *arg, int ldarg, hipStream_t s);
+hipError_t launch_spmm_reduce_dval(const Geometry &g, const DeviceArrays &d, int value_type, const void *X, int ldx, int k,
+                                   const void *dY, int lddy, const int32_t *arg, int ldarg, void *dval, hipStream_t s);
+hipError_t launch_spmm_reduce_dx(const Geometry &gt, const DeviceArrays &dt, const uint32_t *map, int value_type, int weighted, int k,
+                                 const void *dY, int lddy, const int32_t *arg, int ldarg, void *dX, int lddx, hipStream_t s);
 // ---- attention on the pattern (csr5_attention*.hip) ----
 // One call of the forward, whatever the variant: `heads` heads on packed operands (head h in columns h k .. of Q and K, h d .. of V
 // and O; heads = 1 is the single-head call).  groups: the head groups over grid.y, 0 for the rule, a function of (m, heads).  The

@@ -231,6 +231,90 @@ class anonymouslibHandle:
         """csr5hip_sddmm on raw device pointers (or tensors): U with leading dimension ldu, V with ldv, out nnz values"""
         return self._lib.csr5hip_sddmm(self._h, _ptr(U), int(ldu), _ptr(V), int(ldv), int(k), _ptr(out))
 
+    # -- max / min aggregation on the pattern (csr5hip_reduce.h csr5hip_spmm_reduce) ----------------
+    _REDUCE_OPS = {"max": _capi.REDUCE_MAX, "min": _capi.REDUCE_MIN}
+
+    def _reduce_matrix(self, who: str, name: str, t, rows: int, dt: str, k=None) -> int:
+        """the checks of ``_spmm_args`` for one (rows, k) operand of dtype ``dt``, but for the device, which ``_reduce_apart`` judges
+        after every operand's shape: its leading dimension, or ValueError"""
+        if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+            raise ValueError(f"{who}: {name} must be a torch tensor")
+        if str(t.dtype) != dt:
+            raise ValueError(f"{who}: {name} has dtype {t.dtype}, expected {dt}")
+        if t.dim() != 2 or t.shape[0] != rows or (k is not None and t.shape[1] != k):
+            raise ValueError(f"{who}: {name} must have shape ({rows}, {'k' if k is None else k}), not {tuple(t.shape)}")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{who}: {name} must be row-major with stride(1) == 1, not {t.stride()}")
+        if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+            raise ValueError(f"{who}: {name} rows overlap (stride(0) {t.stride(0)} < k = {t.shape[1]})")
+        return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+    @staticmethod
+    def _reduce_apart(who: str, outs, ins) -> None:
+        """ValueError when an output shares storage with an input or with another output, a tensor does not live on the GPU, or the
+        tensors live on several devices"""
+        named = [p for p in outs + ins if p[1] is not None]
+        for i, (name, t) in enumerate(outs):
+            if t is None:
+                continue
+            for other, u in outs[i + 1:] + ins:
+                if u is not None and _aliased(t, u):
+                    raise ValueError(f"{who}: {name} shares storage with {other} (aliased)")
+        for name, t in named:
+            if t.device.type != "cuda":
+                raise ValueError(f"{who}: {name} must live on the GPU, not {t.device}")
+        if any(t.device != named[0][1].device for _, t in named):
+            raise ValueError(f"{who}: " + ", ".join(f"{name} on {t.device}" for name, t in named))
+
+    def spmmReduce(self, X, Y, reduce="max", arg=None, weighted=True) -> int:
+        """Y[i, c] = max (``reduce="max"``) or min (``"min"``) over row i's stored entries e of a_e * X[col(e), c] -- of X[col(e), c]
+        with ``weighted=False``, which does not read the handle's values -- and arg[i, c] = the winning entry's rank in CSR order
+        (csr5hip_reduce.h: NaN first, then the value, then the smaller rank; a row without entries gets +0 and -1).  X (n, k) and
+        Y (m, k) as ``spmm``'s operands; ``arg`` an int32 (m, k) tensor with stride(1) == 1, or None.  Every row of Y and arg is
+        written.  Wrong dtype, device, shape, stride, ``reduce`` name or an output that shares storage with another operand raise
+        ValueError before the library is called."""
+        who = "spmmReduce"
+        if reduce not in self._REDUCE_OPS:
+            raise ValueError(f"{who}: reduce must be 'max' or 'min', not {reduce!r}")
+        dt = self._dtype_name()
+        ldx = self._reduce_matrix(who, "X", X, self._n, dt)
+        k = int(X.shape[1])
+        ldy = self._reduce_matrix(who, "Y", Y, self._m, dt, k)
+        ldarg = k if arg is None else self._reduce_matrix(who, "arg", arg, self._m, "torch.int32", k)
+        self._reduce_apart(who, [("Y", Y), ("arg", arg)], [("X", X)])
+        return self.spmm_reduce_ptr(self._REDUCE_OPS[reduce], int(bool(weighted)), X, ldx, k, Y, ldy, arg, ldarg)
+
+    def spmm_reduce_ptr(self, op: int, weighted: int, X, ldx: int, k: int, Y, ldy: int, arg, ldarg: int) -> int:
+        """csr5hip_spmm_reduce on raw device pointers (or tensors)"""
+        return self._lib.csr5hip_spmm_reduce(self._h, int(op), int(weighted), _ptr(X), int(ldx), int(k), _ptr(Y), int(ldy), _ptr(arg),
+                                             int(ldarg))
+
+    def spmmReduceBackward(self, X, dY, arg, dX=None, dVal=None, weighted=True) -> int:
+        """The gradients of ``spmmReduce``'s Y from its ``arg`` and dY (m, k): dX (n, k), every row written, by a column kernel on the
+        transposed companion (``buildTranspose`` first; no atomics), and -- ``weighted`` only -- dVal, nnz values in CSR order.
+        Either may be None and is then not computed.  X is read for dVal only (None is allowed without it).  The checks are
+        ``spmmReduce``'s."""
+        who = "spmmReduceBackward"
+        dt = self._dtype_name()
+        lddy = self._reduce_matrix(who, "dY", dY, self._m, dt)
+        k = int(dY.shape[1])
+        ldarg = self._reduce_matrix(who, "arg", arg, self._m, "torch.int32", k)
+        if X is None and dVal is not None:
+            raise ValueError(f"{who}: dVal needs X")
+        ldx = k if X is None else self._reduce_matrix(who, "X", X, self._n, dt, k)
+        lddx = k if dX is None else self._reduce_matrix(who, "dX", dX, self._n, dt, k)
+        if dVal is not None:
+            if not weighted:
+                raise ValueError(f"{who}: dVal exists only with weighted=True")
+            self._csr_value_args(who, (("dVal", dVal),))
+        self._reduce_apart(who, [("dX", dX), ("dVal", dVal)], [("X", X), ("dY", dY), ("arg", arg)])
+        return self.spmm_reduce_backward_ptr(int(bool(weighted)), X, ldx, k, dY, lddy, arg, ldarg, dX, lddx, dVal)
+
+    def spmm_reduce_backward_ptr(self, weighted: int, X, ldx: int, k: int, dY, lddy: int, arg, ldarg: int, dX, lddx: int, dVal) -> int:
+        """csr5hip_spmm_reduce_backward on raw device pointers (or tensors)"""
+        return self._lib.csr5hip_spmm_reduce_backward(self._h, int(weighted), _ptr(X), int(ldx), int(k), _ptr(dY), int(lddy), _ptr(arg),
+                                                      int(ldarg), _ptr(dX), int(lddx), _ptr(dVal))
+
     # -- attention on the pattern: what the twelve wrappers below share (DESIGN.md section 28) ------
     def _forward_operands(self, Q, K, V, O):
         """(ins, outs) of a forward for ``_operand_args``: (name, tensor, rows, which width) each"""

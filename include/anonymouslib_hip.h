@@ -138,6 +138,22 @@ public:
     {
         return _h ? csr5hip_spmm(_h, (const void *)X, ldx, k, (void *)Y, ldy) : _err;
     }
+    // extension: Y[i, c] = the maximum (op = CSR5HIP_REDUCE_MAX) or minimum (CSR5HIP_REDUCE_MIN) over row i's stored entries e of
+    // a_e * X[col(e), c] (weighted = 1) or of X[col(e), c] (weighted = 0), and arg[i, c] = the winning entry's CSR rank (-1 and +0 for
+    // a row without entries); arg may be null; device pointers (csr5hip_reduce.h csr5hip_spmm_reduce)
+    int spmmReduce(int op, int weighted, const ANONYMOUSLIB_VT *X, int ldx, int k, ANONYMOUSLIB_VT *Y, int ldy, int32_t *arg, int ldarg)
+    {
+        return _h ? csr5hip_spmm_reduce(_h, op, weighted, (const void *)X, ldx, k, (void *)Y, ldy, arg, ldarg) : _err;
+    }
+    // extension: its gradients from the forward's arg and dY (m x k): dX (n x k; needs buildTranspose) and, weighted only, dval (nnz
+    // values in CSR order); either may be null (csr5hip_spmm_reduce_backward)
+    int spmmReduceBackward(int weighted, const ANONYMOUSLIB_VT *X, int ldx, int k, const ANONYMOUSLIB_VT *dY, int lddy,
+                           const int32_t *arg, int ldarg, ANONYMOUSLIB_VT *dX, int lddx, ANONYMOUSLIB_VT *dval)
+    {
+        return _h ? csr5hip_spmm_reduce_backward(_h, weighted, (const void *)X, ldx, k, (const void *)dY, lddy, arg, ldarg, (void *)dX,
+                                                 lddx, (void *)dval)
+                  : _err;
+    }
     // extension: new values (nnz of them, CSR order, device pointer, not the array given to inputCSR) under the same pattern,
     // without a new conversion (csr5hip.h csr5hip_update_values)
     int updateValues(const ANONYMOUSLIB_VT *val) { return _h ? csr5hip_update_values(_h, (const void *)val) : _err; }

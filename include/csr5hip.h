@@ -695,6 +695,7 @@ int csr5hip_multi_destroy(csr5hip_multi mh);
 #include "csr5hip_gat.h"
 #include "csr5hip_dropout.h"
 #include "csr5hip_dropout_lowp.h"
+#include "csr5hip_reduce.h"
 
 #ifdef __cplusplus
 }
